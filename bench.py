@@ -14,6 +14,11 @@ no collective inside the loop, one RCCL all-reduce of a small statistics vector 
 
 Prints ONE JSON line on rank 0.  `value` = instance control-steps/s over all GPUs
 (= batch x batched-steps/s; `batched_steps_per_s` is reported beside it).
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full adds what takes work of its own:
+the CPU baseline (--cpu-sample instances, measured before the first GPU call), the HBM read probe and the posterior
+kernel with the device to itself (after the timed region).  --dump-outputs DIR writes what the last timed step
+computed (rank 0's instances) as DIR/<name>.npy.
 """
 import argparse
 import glob
@@ -56,7 +61,12 @@ def parse():
     ap.add_argument("--ntrain", type=int, default=512)
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32")
     ap.add_argument("--variant", default="dense")
-    ap.add_argument("--cpu-sample", type=int, default=4096, help="instances timed for the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=4096, help="instances timed for the CPU baseline with --full (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what a plain run leaves out: the CPU baseline, the HBM read probe and the posterior "
+                         "kernel with the device to itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--parts", type=int, default=0,
                     help="part batches, each on its own HIP stream (ops.ConcurrentControlLoop): one part's solve launch "
                          "runs beside the other parts' posterior streams; 1 = the whole batch on one stream.  0 (default) = the "
@@ -76,8 +86,11 @@ def parse():
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--config", choices=["c3", "c4", "c5", "learn"], default="c3")
     pre.add_argument("--gpus", type=int, default=1)
+    pre.add_argument("--full", action="store_true")          # c3 only: not handed to the other harnesses
     pargs, rest = pre.parse_known_args()
     if pargs.config != "c3":
+        if pargs.full:
+            sys.stderr.write("bench.py: --full applies to --config c3 only; ignored for --config %s\n" % pargs.config)
         pargs.rest = rest
         return pargs
     args = ap.parse_args()
@@ -330,6 +343,29 @@ def cpu_baseline(sample, N, n, m, seed=1234, task_seed=99):
                 cpu_model=cpu_model(), host_threads=ncpu, usable_cpus=usable, usable_cpus_how=usable_how, variants=variants)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, ws, x):
+    """What a caller of the timed path receives after its last step, as <path>/<name>.npy: the control `y` [B, m+1] (u and
+    the relaxation), solver `status` / `iters`, the advanced state `x_next`, and the posterior `Mk` / `Bk` of that step.
+    Floating arrays keep the run's precision, integer ones are written as float32 (exact).  Above 64 MB in all, a fixed
+    seeded sample of instances is written instead, its indices as `sample_index`."""
+    arrays = {"y": ws["y"], "status": ws["status"], "iters": ws["iters"], "x_next": x, "Mk": ws["Mk"], "Bk": ws["Bk"]}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in arrays.items()}
+    B = arrays["y"].shape[0]
+    per_instance = sum(v.nbytes for v in arrays.values()) / float(B)
+    if per_instance * B > DUMP_LIMIT_BYTES:
+        keep = int(DUMP_LIMIT_BYTES // (per_instance + 8))          # + 8: the float64 index of each kept instance
+        idx = np.sort(np.random.default_rng(20240601).choice(B, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(v[idx]) for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher: N ranks (one process per GPU) under torch.distributed.run as a CHILD
     process; this parent never touches the GPU (bayesian_cbf_amd.distributed.launch_ranks)."""
@@ -352,7 +388,7 @@ def main():
     # the CPU baseline (rank 0 of a one-GPU run) is measured FIRST: its process-per-core variant forks workers, which must
     # happen before this process initialises the GPU
     cpu_base = None
-    if world == 1 and rank == 0 and args.cpu_sample > 0 and args.regime == "independent":
+    if args.full and world == 1 and rank == 0 and args.cpu_sample > 0 and args.regime == "independent":
         cpu_base = cpu_baseline(args.cpu_sample, args.ntrain, 3, 2, seed=1234 + rank, task_seed=99 + rank)
     # test hooks (one-GPU boxes): BCBF_BENCH_SINGLE_DEVICE=1 puts every rank on cuda:0, BCBF_BENCH_BACKEND=gloo
     # replaces RCCL -- the N>1 code path is then exercised without a second GPU
@@ -426,6 +462,7 @@ def main():
                                          max_iters=20)
         ev_stream = loop.streams
         step, status_t, iters_t = loop.step, loop.status, loop.iters
+        ws = loop.ws
     else:
         ws = ops.control_workspace(Bt, 2, dtype, dev)
         one = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=dt_plant, L_true=L_true, L_mean=L_mean, clf_gamma=10.0,
@@ -467,6 +504,8 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ws, x)
     # per-launch duration (what a kernel trace reports), and the time during which AT LEAST ONE launch of the kernel
     # was executing (with one stream the two coincide; with concurrent parts the launches overlap one another, a
     # launch's own duration then includes the time it shared the device, and bytes / union time is the rate the
@@ -565,7 +604,7 @@ def main():
         # the same kernel on the same part batch with the device to itself (after the timed region): one launch per event
         # pair, nothing else running -- bytes per launch / its own duration, the figure a kernel trace of a one-stream run gives
         alone = {}
-        if S > 1:
+        if args.full and S > 1:
             for tag, cnt in (("part_batch", Bcs[0]), ("full_batch", Bt)):
                 sl = slice(0, cnt)
                 pa = [gp[k][sl] for k in ("Lop", "Vw", "X", "UHB", "ell", "s2", "Bm", "M0")] + [x[sl].contiguous()]
@@ -617,12 +656,13 @@ def main():
         # launch by bcbf_hbm_read_probe (same 16-byte non-temporal loads, no arithmetic), ONE stream, after the timed region.  It is a
         # reference point, not a ceiling: the headline's four staggered part-batch launches have measured a few percent ABOVE this
         # one-stream probe (round 5: 7.29 against 7.02 TB/s), so no "fraction of measured peak" is derived from it.
-        probe = ops.hbm_read_probe(Lop, launches=10)
-        out["roofline"]["read_probe"] = dict(
-            gbs=probe["best_gbs"], mean_gbs=probe["mean_gbs"],
-            how="bcbf_hbm_read_probe: read-only pass over the %.2f GB operator buffer on one stream, best of %d launches, device to "
-                "itself, after the timed region; NOT an upper bound (overlapping launches on several streams read faster); `peak` / "
-                "`frac` are on the vendor figure" % (probe["bytes"] / 1e9, probe["launches"]))
+        if args.full:
+            probe = ops.hbm_read_probe(Lop, launches=10)
+            out["roofline"]["read_probe"] = dict(
+                gbs=probe["best_gbs"], mean_gbs=probe["mean_gbs"],
+                how="bcbf_hbm_read_probe: read-only pass over the %.2f GB operator buffer on one stream, best of %d launches, "
+                    "device to itself, after the timed region; NOT an upper bound (overlapping launches on several streams read "
+                    "faster); `peak` / `frac` are on the vendor figure" % (probe["bytes"] / 1e9, probe["launches"]))
         if alone:
             alone["note"] = ("the same kernel with the device to itself, one launch per HIP-event pair, after the timed region: "
                              "algorithmic bytes per launch / that launch's duration (what a kernel trace of a one-stream run "

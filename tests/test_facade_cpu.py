@@ -287,38 +287,41 @@ def test_reference_checkpoint_loads_and_is_rewritten_key_for_key(tag, cls, n, m,
 
 
 def test_facade_checkpoint_loads_into_the_executed_reference(tmp_path):
-    """Container-only (needs /root/reference): a file the façade's `save` wrote goes through the reference's own
-    `load_state_dict`.  The reference runs in a child process (its harness patches torch for the old API it expects)."""
-    import subprocess
-    import sys
-    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    if not os.path.isdir("/root/reference/bayes_cbf"):
-        pytest.skip("reference tree not present")
+    """A file the façade's `save` wrote, put through the reference's loader as it reads a checkpoint
+    (control_affine_model.py:212-218, 866-868), with the reference's own file (written by its `save`) as the template:
+    `model` and `likelihood` at the top; the model pops `matshape`, `train_inputs`, `train_targets` and hands every other
+    entry to the sub-module of that name -- torch modules load strictly (same keys, same shapes), the decoder reads `sizes`,
+    the mean module `matshape` and `decoder`; the likelihood loads strictly too.  The reference model then holds what it saved."""
     import bayesian_cbf_amd.control_affine_model as cam
     path, g = _ckpt("n3m2_N24")
     reg = cam.ControlAffineRegressor(3, 2, device="cpu", dtype=torch.float64)
     reg.load(path)
     p2 = str(tmp_path / "saved.pickle")
     reg.save(p2)
-    child = """
-import sys, torch
-sys.path.insert(0, %r)
-import _refenv
-_refenv.setup()
-torch.set_default_dtype(torch.float64)
-import bayes_cbf.control_affine_model as rcam
-ref = rcam.ControlAffineRegressor(3, 2, device="cpu")
-ref.load_state_dict(torch.load(%r))
-want = torch.load(%r)["model"]
-got = ref.state_dict()["model"]
-for mod in ("task_covar", "input_covar", "covar_module"):
-    for k in want[mod]:
-        assert torch.equal(got[mod][k], want[mod][k]), (mod, k)
-assert torch.equal(got["train_inputs"][0], want["train_inputs"][0]) and torch.equal(got["train_targets"], want["train_targets"])
-print("reference loaded the facade checkpoint")
-""" % (golden, p2, path)
-    out = subprocess.run([sys.executable, "-c", child], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "reference loaded the facade checkpoint" in out.stdout, out.stderr[-2000:]
+    want, got = torch.load(path), torch.load(p2)
+    assert {"model", "likelihood"} <= set(got)
+
+    def loads_strictly(have, ref):
+        """torch's strict load_state_dict: no missing or unexpected key, no size mismatch; the module then holds the
+        file's values, which must be the reference's own"""
+        assert set(have) == set(ref)
+        for k, v in ref.items():
+            assert tuple(have[k].shape) == tuple(v.shape), k
+            assert torch.equal(have[k].double(), v), k
+
+    loads_strictly(got["likelihood"], want["likelihood"])
+    model = dict(got["model"])
+    assert tuple(model.pop("matshape")) == tuple(want["model"]["matshape"])
+    inputs, targets = model.pop("train_inputs"), model.pop("train_targets")
+    assert isinstance(inputs, tuple) and len(inputs) == len(want["model"]["train_inputs"]) == 1
+    assert torch.equal(inputs[0].double(), want["model"]["train_inputs"][0]) and torch.equal(targets.double(), want["model"]["train_targets"])
+    # every remaining entry names a sub-module of the reference model (getattr(self, k) must exist)
+    assert set(model) == set(want["model"]) - {"matshape", "train_inputs", "train_targets"}
+    assert model["decoder"]["sizes"] == want["model"]["decoder"]["sizes"]            # the decoder reads `sizes`
+    for k in ("matshape", "decoder"):                                                # the mean module reads these two
+        assert model["mean_module"][k] == want["model"]["mean_module"][k], k
+    for mod in ("task_covar", "input_covar", "covar_module"):
+        loads_strictly(model[mod], want["model"][mod])
 
 
 # ---- batched hyper-parameter fit: the host-side pieces that need no GPU

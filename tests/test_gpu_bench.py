@@ -30,7 +30,7 @@ def _run(extra_args, extra_env, timeout=600):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    out = _run(["--cpu-sample", "8"], {})
+    out = _run(["--full", "--cpu-sample", "8"], {})
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in out, key
@@ -45,6 +45,35 @@ def test_single_gpu_line_has_the_contract_fields():
     assert abs(total / (rf["kernel_busy_ms_per_step"] * 1e-3) / 1e9 - rf["achieved"]) < 1e-6 * rf["achieved"]
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full: no CPU baseline, no probe launches after the timed region; --dump-outputs writes what the last timed
+    step computed, one array per output, float32 in an f32 run; a second run with the same arguments starts from the same
+    inputs and writes the same arrays; the state has moved away from the initial one."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = _run(["--dump-outputs", str(d)], {})
+        assert out["steps"] == 4 and out["ms_per_step"] > 0 and "cpu_baseline" not in out
+        assert "read_probe" not in out["roofline"] and "unoverlapped" not in out["roofline"]
+        got = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+        assert sorted(got) == ["Bk", "Mk", "iters", "status", "x_next", "y"]
+        shapes = {"y": (256, 3), "status": (256,), "iters": (256,), "x_next": (256, 3), "Mk": (256, 3, 3), "Bk": (256, 3, 3)}
+        for name, v in got.items():
+            assert v.dtype == np.float32 and v.shape == shapes[name] and np.isfinite(v).all(), name
+        assert (got["status"] == 0).mean() == out["solver"]["optimal_fraction"]
+        dumps.append(got)
+    for name in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][name], dumps[1][name], err_msg=name)
+    # the initial state bench.py draws (same generator, seed and device), fetched after both runs
+    import torch
+    from bayesian_cbf_amd.synthetic import make_unicycle_task
+    x0 = make_unicycle_task(256, dtype=torch.float32, device="cuda", seed=99)["x"].cpu().numpy()
+    moved = np.abs(dumps[0]["x_next"] - x0).max(axis=1) > 0
+    solved = dumps[0]["status"] == 0                      # solved in the last step: took a plant step in it
+    assert solved.any() and moved[solved].all()
 
 
 def test_rccl_path_with_one_rank():

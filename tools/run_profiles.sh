@@ -6,7 +6,7 @@ export GPU_MAX_HW_QUEUES=8   # the setting bench.py gives itself; under rocprofv
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$R
 mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --steps 20 --warmup 5 --cpu-sample 0 > $O/bench_driver_form.json 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -- python3 bench.py --steps 100 --warmup 60 --cpu-sample 0 > $O/bench_default_prof.json 2> $O/bench_default_prof.err
 python tools/trace_union.py $O/prof_default $O/bench_default_prof.json $O/bench_default_prof_union.json > $O/union_default.txt 2>&1
