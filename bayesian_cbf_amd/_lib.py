@@ -47,6 +47,7 @@ _TSIGS = {
     "bcbf_unicycle_control_step_observe": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int,
                                            P, P, P, P, c_int, P, c_int, P, P, P],
     "bcbf_potrf": [P, P, P, P, c_int, c_int, P],
+    "bcbf_subsample_rows": [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P],
     "bcbf_potrs": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_chol_append": [P, P, P, P, P, c_int, c_int, P],
     "bcbf_gp_append": [P] * 17 + [c_int, c_int, c_int, c_int, P],

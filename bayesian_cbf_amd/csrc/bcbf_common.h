@@ -46,6 +46,7 @@ template <int V>
 __host__ __device__ inline size_t lop_elems(int Np) { return (size_t)Np * (Np + 2) / 2 + (size_t)NB * Np; }
 
 void set_error(const char* what, hipError_t err);
+void set_error_message(const char* msg);   // an argument check's reason, for bcbf_last_error
 // bcbf_refit_retry: the previous attempt's info[Bt] while the retry's launch is being set up on this host thread (NULL otherwise).
 // Every refit kernel takes it as its last argument: an instance whose entry is 0 returns at once (info[b] = 0 again).
 extern thread_local const int* g_refit_only_bad;

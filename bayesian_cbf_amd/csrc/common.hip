@@ -10,6 +10,9 @@ thread_local const int* g_refit_only_bad = nullptr;
 void set_error(const char* what, hipError_t err) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(err));
 }
+void set_error_message(const char* msg) {
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+}
 int check_launch(const char* what) {
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) { set_error(what, err); return BCBF_ELAUNCH; }

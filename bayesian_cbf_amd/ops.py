@@ -222,6 +222,39 @@ def potrs(Lop, Xdot, UH, M0, want_alpha=True, out_Vw=None):
     return Vw, alpha
 
 
+SUBSAMPLE_MAX_POOL = 8192          # bcbf_subsample_rows sorts the pool in LDS
+
+
+def subsample_rows(keys, X, UH, Y, N, lo=0, P=None, out=None):
+    """Random N-row subset of every instance's pool = stream rows lo .. lo+P-1 of X[B,Ntot,n], UH[B,Ntot,1+m], Y[B,Ntot,n]
+    (bcbf_subsample_rows): the reference's shuffle of the whole buffer + first max_train (unicycle_move_to_pose.py:377-384)
+    with the caller's draws keys[B, >=P] (fp32 uniform in [0,1), for both precisions).  Output row j = the pool row with the
+    j-th smallest key, ties to the lower index: idx == torch.sort(keys[:, :P], stable=True).indices[:, :N] + lo.
+    Returns (Xo[B,N,n], UHo[B,N,1+m], Yo[B,N,n], idx[B,N] int32 stream rows); out = the same four buffers to write into."""
+    _chk(X, UH, Y)
+    _chk(keys)
+    if keys.dtype != torch.float32 or keys.device != X.device or keys.dim() != 2:
+        raise TypeError("subsample_rows: keys must be a [B, >=P] float32 tensor on the streams' device")
+    B, Ntot, n = X.shape
+    C = UH.shape[2]
+    P = Ntot - lo if P is None else int(P)
+    if UH.shape[:2] != (B, Ntot) or Y.shape != (B, Ntot, n) or keys.shape[0] != B:
+        raise ValueError("subsample_rows: X %s, UH %s, Y %s, keys %s" % (tuple(X.shape), tuple(UH.shape), tuple(Y.shape), tuple(keys.shape)))
+    f = dict(dtype=X.dtype, device=X.device)
+    if out is None:
+        out = (torch.empty(B, N, n, **f), torch.empty(B, N, C, **f), torch.empty(B, N, n, **f),
+               torch.empty(B, N, dtype=torch.int32, device=X.device))
+    Xo, UHo, Yo, idx = out
+    _chk(X, Xo, UHo, Yo, idx)
+    if Xo.shape != (B, N, n) or UHo.shape != (B, N, C) or Yo.shape != (B, N, n) or idx.shape != (B, N) or idx.dtype != torch.int32:
+        raise ValueError("subsample_rows: output buffers of the wrong shape / dtype")
+    rc = getattr(lib, "bcbf_subsample_rows" + _suf(X))(_p(keys), keys.shape[1], lo, P, _p(X), _p(UH), _p(Y), Ntot, n, C - 1, N,
+                                                       _p(Xo), _p(UHo), _p(Yo), _p(idx), B, _stream(X))
+    if rc != 0:
+        raise _lib.BcbfError("bcbf_subsample_rows failed (rc=%d): %s" % (rc, lib.bcbf_last_error().decode()))
+    return Xo, UHo, Yo, idx
+
+
 def chol_append(Lop, knew, kappa, N):
     _chk(Lop, knew, kappa)
     Bt = Lop.shape[0]

@@ -595,11 +595,22 @@ def final_window_vs_device_refit(final, sample=64):
                 Bk=float(((f64(Bk[idx]) - Br).abs().amax(dim=(1, 2)) / prior).max()))
 
 
+def subsample_pool(window, own_rows, max_train):
+    """Which stream rows a refit of `self_learning_closed_loop(subsample="random")` learns from, when the instance has made
+    `own_rows` observations (stream rows window .. window + own_rows - 1; rows 0 .. window-1 are the synthetic start).
+    Returns (lo, P, random): up to max_train own rows, the last `window` rows [lo, lo + P) themselves (synthetic start rows
+    included, as subsample="window"); beyond, the reference's `XdotTrain.shape[0] > max_train` branch
+    (unicycle_move_to_pose.py:377-384): a random max_train-subset of ALL own rows, the pool [window, window + own_rows)."""
+    if own_rows <= max_train:
+        return own_rows, window, False
+    return window, own_rows, True
+
+
 def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40, warmup=None, dtype=torch.float32, device="cuda",
                               seed=1234, schedule="reference", parts=4, stagger=True, shift_invariant=True, dt=0.01,
                               retry_levels=3, fit_iters=0, fit_lr=0.1, fit_dtype=torch.float64, record_states=False, barrier=None,
                               mid_period_steps=0, query_shift_invariant=True, level_decay_every=4, factor_dtype=None,
-                              min_jitter_level=1e-5):
+                              min_jitter_level=1e-5, subsample="window"):
     """The reference's learning loop for MANY instances, fed BY ITSELF (LearnedShiftInvariantDynamics.train / fit,
     unicycle_move_to_pose.py:326-386): every control step's observation row is built on the device from the loop's own
     (x_t, u_t, x_{t+1}) -- inside the solve / plant launch (`bcbf_unicycle_control_step_observe`): regressor input = the state
@@ -641,8 +652,19 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
     variance below ~sqrt(cond K_b) eps32 of the prior: with fp64 factors at the 1e-5 level B_k = s2 B - W'W is rounding noise (it
     goes indefinite and the cone conversion refuses the program); 1e-3 keeps it resolvable.
 
+    subsample (schedule "reference"): which rows a refit learns from.
+      "window" (default): the last `max_train` observations, a sliding window (the figures in DESIGN 3.4 are this mode's).
+      "random": the reference's training set (LearnedShiftInvariantDynamics.fit, unicycle_move_to_pose.py:377-384): while an
+                instance has made at most max_train observations, the window as above; beyond, a FRESH random max_train-subset
+                of all its own observations at every refit (`subsample_pool`) -- keys rand(Bt_c, P) from the loop's generator,
+                `bcbf_subsample_rows` sorts them and gathers the chosen rows into per-part subset buffers on the device (no host
+                round trip), which the refit (and the fit) reads.  The draws come from the loop's torch generator, not from
+                numpy's global RNG: the distribution of the subset is the reference's, the sample is not.  The pool holds at
+                most warmup + steps + mid_period_steps rows, which the kernel limits to 8192.
+
     Returns (report, final): final = dict(rows = the raw observation rows each instance's model holds, oldest first
-    (X, UH, Y, jitter [Bt, N, .]), posterior = (Mk, Bk) of the final model at `xq_check`, xq_check, hyper-parameters; states
+    (X, UH, Y, jitter [Bt, N, .]; subsample="random": in subset order, with `subset_index` [Bt, N] int32 = their stream rows),
+    posterior = (Mk, Bk) of the final model at `xq_check`, xq_check, hyper-parameters; states
     (record_states): the visited (x_t, u_t) of every step)."""
     import time
     from .synthetic import make_instances, make_unicycle_task
@@ -654,6 +676,11 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
         raise ValueError("steps must be a positive multiple of refit_every")
     if fit_iters and schedule != "reference":
         raise ValueError("fit_iters: the hyper-parameter fit rides on the reference schedule's refits")
+    if subsample not in ("window", "random"):
+        raise ValueError("subsample: 'window' or 'random'")
+    if subsample == "random" and schedule != "reference":
+        raise ValueError("subsample='random' needs schedule='reference' (a bordered factor cannot drop rows)")
+    randsub = subsample == "random"
     online = schedule == "online_tail"
     window = max_train - refit_every if online else max_train
     if window < 1:
@@ -663,6 +690,9 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
     warmup = -(-warmup // refit_every) * refit_every
     total = warmup + steps + int(mid_period_steps)
     Ntot = window + total + 1
+    if randsub and total > ops.SUBSAMPLE_MAX_POOL:
+        raise ValueError("subsample='random': a refit's pool (up to warmup + steps + mid_period_steps = %d rows) exceeds the "
+                         "kernel's %d" % (total, ops.SUBSAMPLE_MAX_POOL))
     p = make_instances(Bt, window, n, m, dtype=dtype, device=dev, seed=seed, variant="theta" if shift_invariant else "dense")
     task = make_unicycle_task(Bt, dtype=dtype, device=dev, seed=seed + 99)
     f = dict(dtype=dtype, device=dev)
@@ -772,6 +802,11 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
                                                              observe=obs_kw)
                            for b_ in pt.bufs]
                 pt.lo = 0
+                pt.pool_rows = window
+                if randsub:
+                    # the rows the current model was factored from, in subset order, with their jitter (pt.J stays per stream row)
+                    pt.sX, pt.sUH, pt.sY, pt.sJ = Xw, UHw, Yw, Jw
+                    pt.sidx = torch.arange(window, dtype=torch.int32, device=dev).expand(pt.Bt, window).contiguous()
                 if fit_iters:
                     from .batched_fit import BatchedHyperFit
                     pt.bf = BatchedHyperFit.from_values(pt.hp["A"], pt.hp["Bm"], pt.hp["ell"], pt.hp["s2"], pt.hp["M0"], dtype=fit_dtype)
@@ -803,15 +838,28 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
     refit_log = []
 
     def do_refit(c, pt, t):
-        """Part c, after step t: refactor the last `window` observations into the buffer that is not being read; swap."""
+        """Part c, after step t: refactor the last `window` observations (subsample="random": the rows `subsample_pool` picks)
+        into the buffer that is not being read; swap."""
         lo = t + 1
+        if randsub:
+            lo, pt.pool_rows, drawn = subsample_pool(window, t + 1, max_train)
         cutw = lambda t_: t_[:, lo:lo + window].contiguous()
-        Xw, UHw, Yw = cutw(pt.X), cutw(pt.UH), cutw(pt.Y)
+        if not randsub:
+            Xw, UHw, Yw = cutw(pt.X), cutw(pt.UH), cutw(pt.Y)
         # a fresh jitter draw per factorisation, at the instance's level: one below the one that last worked (make_psd, :903-919)
         pt.n_refits += 1
         if level_decay_every and pt.n_refits % level_decay_every == 0:
             pt.level.div_(10).clamp_(min=float(min_jitter_level))
         Jw = (pt.level[:, None] * rnd(pt.Bt, window)).contiguous()
+        if randsub:
+            if drawn:
+                keys = torch.rand(pt.Bt, pt.pool_rows, generator=gen, dtype=torch.float32, device=dev)
+                ops.subsample_rows(keys, pt.X, pt.UH, pt.Y, window, lo=lo, P=pt.pool_rows, out=(pt.sX, pt.sUH, pt.sY, pt.sidx))
+            else:
+                pt.sX.copy_(pt.X[:, lo:lo + window]); pt.sUH.copy_(pt.UH[:, lo:lo + window]); pt.sY.copy_(pt.Y[:, lo:lo + window])
+                pt.sidx.copy_(torch.arange(lo, lo + window, dtype=torch.int32, device=dev).expand(pt.Bt, window))
+            pt.sJ.copy_(Jw)
+            Xw, UHw, Yw, Jw = pt.sX, pt.sUH, pt.sY, pt.sJ
         if fit_iters:
             wd = fit_dtype
             pt.bf.fit(Xw.to(wd), UHw[:, :, 1:].to(wd).contiguous(), Yw.to(wd), training_iter=fit_iters, lr=fit_lr)
@@ -820,7 +868,8 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
                 pt.hp[k].copy_(hp[k].to(dtype))
         nxt = 1 - pt.cur
         pt.factor_into(pt.bufs[nxt], Xw, UHw, Yw, Jw)
-        pt.J[:, lo:lo + window] = Jw                                  # the level every point was finally factored with
+        if not randsub:
+            pt.J[:, lo:lo + window] = Jw                              # the level every point was finally factored with
         pt.cur, pt.lo = nxt, lo
 
     t0 = None
@@ -894,7 +943,8 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
                   refit_failures_after_retries=int(sum(int(pt.fail_count) for pt in P)) + (sum(g.rgp.count_drop_failures() for g in P) if online else 0),
                   instances_factored_per_retry_level=[int(v) for v in sum((pt.rgp.retry_counts if online else pt.retry_counts) for pt in P).tolist()],
                   jitter_level_max=float(max(float((pt.rgp.jitter_level if online else pt.level).max()) for pt in P)),
-                  solver_optimal_fraction=float((ws["status"] == 0).float().mean()))
+                  solver_optimal_fraction=float((ws["status"] == 0).float().mean()), subsample=subsample,
+                  pool_rows_at_last_refit=[pt.pool_rows for pt in P] if not online else None)
     if not online:
         pass_bytes = isz * (window * (window + 1) // 2 + 2 * window * n + window * (1 + m)) * Bt
         report["roofline"] = {"pass": dict(bound="hbm", kernel="posterior_step_kernel<%s, 3, 4, 0, 1, false, 0>" % ("float" if isz == 4 else "double"),
@@ -913,6 +963,10 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
                 rowsX.append(g.X[:, :g.N].clone()); rowsUH.append(g._rUH[:, :g.N].clone())
                 rowsY.append(g._rY[:, :g.N].clone()); rowsJ.append(g._rJ[:, :g.N].clone())
                 Mk, Bk = g.posterior(xqc)
+            elif randsub:
+                rowsX.append(pt.sX.clone()); rowsUH.append(pt.sUH.clone()); rowsY.append(pt.sY.clone()); rowsJ.append(pt.sJ.clone())
+                b_ = pt.bufs[pt.cur]
+                Mk, Bk = ops.posterior_step(b_["Lop"], b_["Vw"], b_["X"], b_["UHB"], pt.hp["ell"], pt.hp["s2"], pt.hp["Bm"], pt.hp["M0"], xqc)
             else:
                 sl_ = slice(pt.lo, pt.lo + window)
                 rowsX.append(pt.X[:, sl_].clone()); rowsUH.append(pt.UH[:, sl_].clone())
@@ -925,6 +979,8 @@ def self_learning_closed_loop(Bt=4096, max_train=512, steps=200, refit_every=40,
     final["bounds"] = bounds
     final["posterior"] = (torch.cat(Mks, 0), torch.cat(Bks, 0))
     final["stream_rows"] = dict(X=Xall, UH=UHall, Y=Yall, jitter=Jall, window=window)
+    if randsub:
+        final["subset_index"] = torch.cat([pt.sidx for pt in P], 0)
     if record_states:
         final["states"] = dict(x=torch.stack(xs_log, 1), u=torch.stack(us_log, 1))
     return report, final

@@ -129,6 +129,21 @@ int bcbf_refit_retry_kind_f64(const double* X, const double* UH, const double* B
                               const double* jitter, double* Lop, double* UHB, const int* prev_info, int* info,
                               int Bt, int N, int n, int m, int kernel_kind, void* stream);
 
+/* Random max_train subset of a learning loop's observation pool, selected and gathered in one launch: the reference's
+ * `np.random.shuffle(indices)` + `shuffled_indices[:max_train]` (LearnedShiftInvariantDynamics.fit,
+ * unicycle_move_to_pose.py:377-384) with the randomness supplied by the caller.  keys[B, ldk]: one draw per pool row (uniform
+ * in [0,1), fp32 for both precisions); the pool of instance b is stream rows lo .. lo+P-1 of X[B,Ntot,n], UH[B,Ntot,1+m],
+ * Y[B,Ntot,n].  Output row j is the pool row with the j-th smallest key, equal keys to the lower pool index first
+ * (= torch.sort(keys[:, :P], stable=True).indices[:, :N] + lo): Xo[B,N,n], UHo[B,N,1+m], Yo[B,N,n] (the layout bcbf_refit /
+ * bcbf_potrs read) and idx_out[B,N] = the stream row of output row j.  Limits: 1 <= N <= P <= 8192, lo + P <= Ntot,
+ * ldk >= P, 1 <= n <= 8, 0 <= m <= 8, B >= 1; otherwise BCBF_EINVAL before any launch, reason in bcbf_last_error. */
+int bcbf_subsample_rows_f32(const float* keys, int ldk, int lo, int P, const float* X, const float* UH, const float* Y,
+                            int Ntot, int n, int m, int N, float* Xo, float* UHo, float* Yo, int32_t* idx_out, int B,
+                            void* stream);
+int bcbf_subsample_rows_f64(const float* keys, int ldk, int lo, int P, const double* X, const double* UH, const double* Y,
+                            int Ntot, int n, int m, int N, double* Xo, double* UHo, double* Yo, int32_t* idx_out, int B,
+                            void* stream);
+
 /* K2 on a caller-supplied dense SPD matrix (lower triangle of Kb[Bt,N,N] is read): same outputs.
  * Replaces torch.linalg.cholesky (control_affine_model.py:911). */
 int bcbf_potrf_f32(const float* Kb, float* Lop, float* Ldense, int* info, int Bt, int N, void* stream);

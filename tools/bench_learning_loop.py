@@ -10,7 +10,9 @@ column share one pass over the window's factor, the points since the last window
 (x_t, u_t, x_{t+1}) inside the solve / plant launch, as LearnedShiftInvariantDynamics.train / fit builds it
 (rollouts.self_learning_closed_loop: part batches on their own streams, host-free refits, staggered); schedules `reference` and
 `online_tail`.  `--fit-iters K` (reference schedule): every refit first runs K Adam iterations of the marginal likelihood for every
-instance (the reference's `fit(..., training_iter=100)`, BatchedHyperFit).  `--data synthetic`: pre-drawn well-conditioned rows
+instance (the reference's `fit(..., training_iter=100)`, BatchedHyperFit).  `--subsample random` (reference schedule): once an
+instance has more than max_train observations, every refit learns from a fresh random max_train-subset of all of them (the
+reference's training set, bcbf_subsample_rows) instead of the last max_train.  `--data synthetic`: pre-drawn well-conditioned rows
 (rollouts.learning_closed_loop; rounds 4-5).
 
     python tools/bench_learning_loop.py                          # 4096 x 512, fp32, 200 timed steps, refit every 40
@@ -43,6 +45,8 @@ ap.add_argument("--dt", type=float, default=0.01)
 ap.add_argument("--retry-levels", type=int, default=3)
 ap.add_argument("--min-jitter-level", type=float, default=1e-5, help="--data loop: floor of the per-instance jitter level (make_psd starts at 1e-5)")
 ap.add_argument("--factor-f64", action="store_true", help="--data loop --dtype f32: factor the windows in fp64, round the operator to fp32 for the passes")
+ap.add_argument("--subsample", choices=["window", "random"], default="window",
+                help="--data loop, reference schedule: which rows a refit learns from (the last max_train, or the reference's random subset)")
 a = ap.parse_args()
 if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or os.environ.get("BCBF_BENCH_FORCE_LAUNCH") == "1"):
     from bayesian_cbf_amd.distributed import launch_ranks
@@ -55,15 +59,20 @@ dtype = torch.float32 if a.dtype == "f32" else torch.float64
 if a.data == "loop":
     if a.schedule == "online":
         raise SystemExit("--data loop: schedules reference | online_tail")
+    if a.subsample == "random" and a.schedule != "reference":
+        raise SystemExit("--subsample random: schedule reference")
     out, final = self_learning_closed_loop(a.batch, a.max_train, a.steps, a.refit_every, warmup=None if a.warmup == 40 else a.warmup,
                                            dtype=dtype, device=ctx.device, seed=1234 + ctx.rank, schedule=a.schedule, parts=a.parts or 4,
                                            stagger=not a.no_stagger, shift_invariant=not a.raw_inputs, dt=a.dt, retry_levels=a.retry_levels,
                                            fit_iters=a.fit_iters, barrier=ctx.barrier,
-                                           factor_dtype=torch.float64 if (a.factor_f64 and a.dtype == "f32") else None, min_jitter_level=a.min_jitter_level)
+                                           factor_dtype=torch.float64 if (a.factor_f64 and a.dtype == "f32") else None, min_jitter_level=a.min_jitter_level,
+                                           subsample=a.subsample)
     chk = final_model_vs_fp64_refit(final)
     nfail = out["refit_failures_after_retries"]
     what = "rows built on the device from the loop's own (x_t, u_t, x_t+1)"
 else:
+    if a.subsample != "window":
+        raise SystemExit("--subsample random: --data loop")
     out, final = learning_closed_loop(a.batch, a.max_train, a.steps, a.refit_every, warmup=a.warmup, dtype=dtype, device=ctx.device,
                                       seed=1234 + ctx.rank, schedule=a.schedule, barrier=ctx.barrier, parts=a.parts or 1)
     chk = final_window_vs_device_refit(final)
