@@ -32,6 +32,9 @@ _SIGS = {
     "bcbf_mll_grad_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bcbf_fit_param_count": (c_int, [c_int, c_int, c_int, c_int]),
     "bcbf_coneqp_f64": (c_int, [P, P, P, P, c_int, c_int, ctypes.POINTER(c_int), c_int, P, P, P, c_int, c_int, P]),
+    "bcbf_pendulum_control_step_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
+                                               ctypes.POINTER(c_double), c_double, P] + [c_double] * 3 + [c_int] * 2
+                                       + [c_double] * 4 + [P] * 24 + [c_int] * 3 + [P] * 3),
 }
 _TSIGS = {
     "bcbf_kb_build": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
@@ -92,6 +95,7 @@ _TSIGS = {
     "bcbf_cbc_socp": [P] * 18 + [c_int, c_int, c_int, c_int, c_int, P],
     "bcbf_unicycle_constraints": [P, P, P, P, "T", P, P, P, P, "T", P, P, P, P, c_int, c_int, P],
     "bcbf_unicycle_step": [P, P, "T", "T", c_int, P],
+    "bcbf_pendulum_plant_step": [P, P, "T", "T", "T", "T", c_int, P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],
     "bcbf_unicycle_control_step": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
     "bcbf_unicycle_control_step_matern52": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],

@@ -1,0 +1,230 @@
+// The pendulum's rel-degree-2 safety loop (SOCPController with cbfs = [RadialCBFRelDegree2], controllers.py:569-591;
+// pendulum.py:643-746), batched: one host call per control step that sequences the existing launchers
+//   jets -> task rows -> cbc2 terms -> pack -> controller cones -> coneqp -> plant step
+// on the caller's stream, as control_step.hip does for the unicycle.  The two kernels of this file are elementwise
+// (one lane per instance); the jets launch dominates the step.
+//
+// Task kernel: the deterministic mean model (a pendulum, or none = ZeroDynamicsModel) is added to the jets' posterior
+// factors exactly as cbc2.reldeg2_quadratic_terms does on the host (Mk += [fhat | ghat], Mj[:, :, (1+i) C] += J[:, :, i]);
+// the radial barrier h = cos(delta) - cos(theta - theta_c) with its gradient and Hessian; the nominal control of
+// controllers.GreedyController (controllers.py:174-213) on the shifted posterior mean; the objective q = e_0, P = 0.
+// Plant kernel: u = y[2:] where the program was solved, u_ref elsewhere (SOCPController.control on a batch); the safety
+// bookkeeping (min_h over h(x_t) before the step, failed programs); x += (f + g u) dt on the true pendulum with the theta
+// wrap of PendulumDynamicsModel.step.
+#include "bcbf_common.h"
+
+namespace bcbf {
+
+template <typename T>
+struct PendulumParams {
+    int has_gp, has_mean, has_uref;
+    T mean_mass, mean_gravity, mean_length;     // deterministic mean model (has_mean)
+    T theta_c, delta_c;                         // RadialCBFRelDegree2: cbf_col_theta, cbf_col_delta
+    T xg[2], Qg[4], R, dt;                      // GreedyController: x_goal, Q (x_quad_goal_cost), R (u_quad_cost), dt
+};
+
+// x <- x + (f(x) + g(x) u) dt,  theta wrapped to [-pi, pi) as ((theta + pi) % 2 pi) - pi with Python's (floored) modulo
+template <typename T>
+__device__ inline void pendulum_euler(T& th, T& om, T u, T mass, T gravity, T length, T dt) {
+    const T xd0 = om;
+    const T xd1 = -(gravity / length) * sin(th) + T(1) / (mass * length) * u;
+    const T tn = th + xd0 * dt;
+    om = om + xd1 * dt;
+    const T two_pi = T(2) * T(M_PI);
+    T r = fmod(tn + T(M_PI), two_pi);
+    if (r < T(0)) r += two_pi;
+    th = r - T(M_PI);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+pendulum_task_kernel(const T* __restrict__ x, T* __restrict__ Mk, T* __restrict__ Bk, T* __restrict__ G,
+                     T* __restrict__ Mj, T* __restrict__ h, T* __restrict__ gh, T* __restrict__ Hh,
+                     const T* __restrict__ u_ref_in, T* __restrict__ u_ref, double* __restrict__ P,
+                     double* __restrict__ q, PendulumParams<T> p, int Bt) {
+    constexpr int n = 2, C = 2, CT = C * (1 + n);
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt) return;
+    const T th = x[b * n], om = x[b * n + 1];
+    T* mk = Mk + (size_t)b * n * C;
+    T* mj = Mj + (size_t)b * n * CT;
+    if (!p.has_gp) {              // no learned model: the mean model is the whole model, every variance term is 0
+        for (int i = 0; i < n * C; ++i) mk[i] = T(0);
+        for (int i = 0; i < n * CT; ++i) mj[i] = T(0);
+        for (int i = 0; i < C * C; ++i) Bk[(size_t)b * C * C + i] = T(0);
+        for (int i = 0; i < CT * CT; ++i) G[(size_t)b * CT * CT + i] = T(0);
+    }
+    if (p.has_mean) {
+        const T c = -(p.mean_gravity / p.mean_length);
+        mk[0 * C + 0] += om;                                 // fhat = [omega, -(g/l) sin theta]
+        mk[1 * C + 0] += c * sin(th);
+        mk[1 * C + 1] += T(1) / (p.mean_mass * p.mean_length);      // ghat = [0, 1/(m l)]'
+        // J[j][i] = d fhat_j / d x_i = [[0, 1], [-(g/l) cos theta, 0]] into column (1+i) C (its zeros add nothing)
+        mj[0 * CT + 2 * C] += T(1);
+        mj[1 * CT + 1 * C] += c * cos(th);
+    }
+    const T d = th - p.theta_c;
+    h[b] = cos(p.delta_c) - cos(d);
+    gh[b * n] = sin(d);
+    gh[b * n + 1] = T(0);
+    Hh[b * 4 + 0] = cos(d);
+    Hh[b * 4 + 1] = Hh[b * 4 + 2] = Hh[b * 4 + 3] = T(0);
+    T u0;
+    if (p.has_uref) {
+        u0 = u_ref_in[b];
+    } else {                     // u = (lam R dt + (1-lam) G'P G)^-1 (1-lam) G'P (x_g - x - f dt),  G = g dt, lam = 1/2
+        const T lam = T(0.5);
+        const T f0 = p.dt * mk[0], f1 = p.dt * mk[C];
+        const T g0 = p.dt * mk[1], g1 = p.dt * mk[C + 1];
+        const T PG0 = g0 * p.Qg[0] + g1 * p.Qg[2], PG1 = g0 * p.Qg[1] + g1 * p.Qg[3];      // (G'P)_j
+        const T Q = lam * (p.R * p.dt) + (T(1) - lam) * (PG0 * g0 + PG1 * g1);
+        const T r0 = p.xg[0] - th - f0, r1 = p.xg[1] - om - f1;
+        const T cc = (T(1) - lam) * (g0 * (p.Qg[0] * r0 + p.Qg[1] * r1) + g1 * (p.Qg[2] * r0 + p.Qg[3] * r1));
+        u0 = cc / Q;
+    }
+    u_ref[b] = u0;
+    for (int i = 0; i < 9; ++i) P[(size_t)b * 9 + i] = 0.0;                  // min y_1: P = 0, q = e_0 (controllers.py:575)
+    q[(size_t)b * 3] = 1.0;
+    q[(size_t)b * 3 + 1] = q[(size_t)b * 3 + 2] = 0.0;
+}
+
+// bcbf_cbc2_terms writes (mean_A, mean_b, Q, p, r, mean(u0), var(u0)); bcbf_controller_cones reads the first five
+template <typename T>
+__global__ void __launch_bounds__(256) pendulum_pack_terms_kernel(const T* __restrict__ t2, T* __restrict__ t, int Bt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt) return;
+    for (int i = 0; i < 5; ++i) t[(size_t)b * 5 + i] = t2[(size_t)b * 7 + i];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int* __restrict__ sstatus,
+                      const int* __restrict__ cstatus, const int* __restrict__ tstatus, const T* __restrict__ u_ref,
+                      const T* __restrict__ h, T* __restrict__ u, int* __restrict__ status, T* __restrict__ min_h,
+                      int* __restrict__ fails, T mass, T gravity, T length, T dt, int Bt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt) return;
+    const int st = tstatus[b] == 1 ? BCBF_PENDULUM_BADHESSIAN : cstatus[b] != 0 ? BCBF_SOCP_BADCONE : sstatus[b];
+    status[b] = st;
+    const T ub = st == 0 ? (T)y[(size_t)b * 3 + 2] : u_ref[b];
+    u[b] = ub;
+    if (min_h) {
+        T hv = h[b];
+        if (!(hv == hv)) hv = -INFINITY;          // a non-finite h never passes for "safe"
+        min_h[b] = hv < min_h[b] ? hv : min_h[b];
+        fails[b] += st != 0;
+    }
+    T th = x[b * 2], om = x[b * 2 + 1];
+    pendulum_euler<T>(th, om, ub, mass, gravity, length, dt);
+    x[b * 2] = th;
+    x[b * 2 + 1] = om;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+pendulum_plant_step_kernel(T* __restrict__ x, const T* __restrict__ u, T mass, T gravity, T length, T dt, int Bt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt) return;
+    T th = x[b * 2], om = x[b * 2 + 1];
+    pendulum_euler<T>(th, om, u[b], mass, gravity, length, dt);
+    x[b * 2] = th;
+    x[b * 2 + 1] = om;
+}
+
+static int pendulum_einval(const char* why) {
+    set_error_message(why);
+    return BCBF_EINVAL;
+}
+
+}  // namespace bcbf
+
+extern "C" {
+#define BCBF_PEND_PLANT(T, SUF)                                                                                       \
+    int bcbf_pendulum_plant_step_##SUF(T* x, const T* u, T mass, T gravity, T length, T dt, int Bt, void* stream) {   \
+        if (!x || !u || Bt < 0) return bcbf::pendulum_einval("pendulum_plant_step: null buffer or Bt < 0");          \
+        if (!(mass * length != T(0)) || !(dt == dt)) return bcbf::pendulum_einval("pendulum_plant_step: m l == 0");  \
+        if (Bt == 0) return BCBF_OK;                                                                                  \
+        hipLaunchKernelGGL((bcbf::pendulum_plant_step_kernel<T>), dim3((Bt + 255) / 256), dim3(256), 0,               \
+                           (hipStream_t)stream, x, u, mass, gravity, length, dt, Bt);                                 \
+        return bcbf::check_launch("pendulum_plant_step");                                                             \
+    }
+BCBF_PEND_PLANT(float, f32)
+BCBF_PEND_PLANT(double, f64)
+#undef BCBF_PEND_PLANT
+
+int bcbf_pendulum_control_step_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
+    using bcbf::pendulum_einval;
+    // ---- argument checks, before any HIP call
+    if (Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
+    if (n != 2 || m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
+    if (!x || !ell || !s2 || !Bm || !A || !kalpha || !x_goal || !Q_goal)
+        return pendulum_einval("pendulum_control_step: null state / model / task buffer");
+    if (!Mk || !Bk || !G || !Mj || !h || !gh || !Hh || !u_ref || !terms2 || !terms || !tstatus || !Gc || !hc ||
+        !cstatus || !P || !q || !y || !sstatus || !u || !status)
+        return pendulum_einval("pendulum_control_step: null workspace buffer");
+    if (!min_h != !fails) return pendulum_einval("pendulum_control_step: min_h and fails go together");
+    if (Lop && (!Vw || !X || !UHB || !M0 || N < 1)) return pendulum_einval("pendulum_control_step: incomplete GP");
+    if (shared != 0 && shared != 1) return pendulum_einval("pendulum_control_step: shared must be 0 or 1");
+    if (kernel_kind < 0 || kernel_kind >= bcbf::BCBF_KINDS) return pendulum_einval("pendulum_control_step: bad kernel_kind");
+    if (hessian_mode != 0 && hessian_mode != 1) return pendulum_einval("pendulum_control_step: bad hessian_mode");
+    if (max_iters < 1) return pendulum_einval("pendulum_control_step: max_iters < 1");
+    if (!(dt > 0.0) || !(R > 0.0)) return pendulum_einval("pendulum_control_step: dt and R must be > 0");
+    if (mean_model && !(mean_mass * mean_length != 0.0)) return pendulum_einval("pendulum_control_step: mean model m l == 0");
+    if (!(true_mass * true_length != 0.0)) return pendulum_einval("pendulum_control_step: true model m l == 0");
+    if (!(safety_factor >= 0.0) || !(ctrl_reg > 0.0) || !(relax_weight > 0.0))
+        return pendulum_einval("pendulum_control_step: safety factor, ctrl_reg, relax_weight");
+    if (Bt == 0) return BCBF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // 1. jets of the learned model at x (skipped without one: the task kernel writes the mean model alone)
+    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+    int rc = BCBF_OK;
+    if (Lop) {
+        auto jets = kernel_kind == 0 ? bcbf_posterior_jets_f64 : kernel_kind == 1 ? bcbf_posterior_jets_matern52_f64
+                                                                                  : bcbf_posterior_jets_rbfm52_f64;
+        rc = jets(Lop, Vw, X, UHB, ell, s2, Bm, M0, x, Mk, Bk, G, Mj, nullptr, shared, Bt, N, 2, 1, stream);
+    }
+    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+    if (rc) return rc;
+    // 2. task kernel
+    bcbf::PendulumParams<double> p;
+    p.has_gp = Lop != nullptr;
+    p.has_mean = mean_model != 0;
+    p.has_uref = u_ref_in != nullptr;
+    p.mean_mass = mean_mass; p.mean_gravity = mean_gravity; p.mean_length = mean_length;
+    p.theta_c = theta_c; p.delta_c = delta_c;
+    p.xg[0] = x_goal[0]; p.xg[1] = x_goal[1];
+    for (int i = 0; i < 4; ++i) p.Qg[i] = Q_goal[i];
+    p.R = R; p.dt = dt;
+    const dim3 grid((Bt + 255) / 256), block(256);
+    hipLaunchKernelGGL((bcbf::pendulum_task_kernel<double>), grid, block, 0, st, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref_in,
+                       u_ref, P, q, p, Bt);
+    if ((rc = bcbf::check_launch("pendulum_task"))) return rc;
+    // 3. rel-degree-2 terms (linearised at u_ref), 4. the program's rows (objective cone + safety cone of kind 1)
+    if ((rc = bcbf_cbc2_terms_f64(Mk, Bk, G, Mj, A, Bm, ell, s2, h, gh, Hh, kalpha, u_ref, terms2, tstatus, Bt, 2, 1,
+                                  hessian_mode, kernel_kind, stream)))
+        return rc;
+    hipLaunchKernelGGL((bcbf::pendulum_pack_terms_kernel<double>), grid, block, 0, st, terms2, terms, Bt);
+    if ((rc = bcbf::check_launch("pendulum_pack_terms"))) return rc;
+    const int kind = 1;
+    if ((rc = bcbf_controller_cones_f64(terms, u_ref, &kind, &safety_factor, ctrl_reg, relax_weight, 2, 1, Gc, hc,
+                                        cstatus, Bt, 1, 1, stream)))
+        return rc;
+    // 5. min y_1 over y = [y_1, rho, u] in Q^3 x Q^3
+    const int qdims[2] = {3, 3};
+    if ((rc = bcbf_coneqp_f64(P, q, Gc, hc, 3, 0, qdims, 2, y, sstatus, iters, Bt, max_iters, stream))) return rc;
+    // 6. choose u, bookkeeping, plant step
+    hipLaunchKernelGGL((bcbf::pendulum_plant_kernel<double>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
+                       h, u, status, min_h, fails, true_mass, true_gravity, true_length, dt, Bt);
+    return bcbf::check_launch("pendulum_plant");
+}
+}

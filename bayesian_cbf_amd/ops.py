@@ -1,6 +1,7 @@
 """Thin host wrappers over the C ABI: torch tensors in, torch tensors out, on the caller's HIP
 stream.  PyTorch is only the allocator / stream provider here; all arithmetic is in libbcbf."""
 import ctypes
+import math
 
 import os
 
@@ -1309,3 +1310,103 @@ def control_workspace(Bt, Kob, dtype, device, n=3, m=2):
                 ghat=torch.empty(Bt, n, m, **f), Mk=torch.empty(Bt, n, 1 + m, **f), Bk=torch.empty(Bt, 1 + m, 1 + m, **f),
                 cones=torch.empty(Bt, K, cone_width(m), **f), cstatus=torch.empty(Bt, K, **i),
                 y=torch.empty(Bt, m + 1, **f), status=torch.empty(Bt, **i), iters=torch.empty(Bt, **i))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The pendulum's rel-degree-2 safety loop (bcbf_pendulum_control_step_f64): SOCPController(cbfs=[RadialCBFRelDegree2],
+# clf=None) with the greedy nominal controller, one host call per step for a batch of pendulums (fp64).
+def pendulum_plant_step(x, u, mass=1.0, gravity=10.0, length=1.0, dt=0.002):
+    """In-place explicit Euler step of the true pendulum with the theta wrap of PendulumDynamicsModel.step; x[Bt,2], u[Bt,1]."""
+    _chk(x, u)
+    check(getattr(lib, "bcbf_pendulum_plant_step" + _suf(x))(_p(x), _p(u), mass, gravity, length, dt, x.shape[0],
+                                                             _stream(x)), "bcbf_pendulum_plant_step")
+    return x
+
+
+def pendulum_workspace(Bt, dtype=torch.float64, device="cuda"):
+    """Caller-owned buffers of `pendulum_control_step` (they also expose the step's intermediates): the jets (Mk, Bk, G, Mj),
+    the barrier (h, gh, Hh), the nominal control u_ref, the terms (terms2 = bcbf_cbc2_terms' row, terms = its packed
+    (bfe, e, V, bfv, v)), the program (Gc[Bt,6,3], hc[Bt,6], P, q), the solve (y = [y_1, rho, u], sstatus, iters) and the
+    outcome (u[Bt,1], status[Bt]: bcbf.h's pendulum status codes)."""
+    if dtype != torch.float64:
+        raise TypeError("the pendulum control step is fp64 (the reference runs this demo in float64)")
+    f = dict(dtype=dtype, device=device)
+    i = dict(dtype=torch.int32, device=device)
+    return dict(Mk=torch.zeros(Bt, 2, 2, **f), Bk=torch.zeros(Bt, 2, 2, **f), G=torch.zeros(Bt, 6, 6, **f),
+                Mj=torch.zeros(Bt, 2, 6, **f), h=torch.empty(Bt, **f), gh=torch.empty(Bt, 2, **f),
+                Hh=torch.empty(Bt, 2, 2, **f), u_ref=torch.empty(Bt, 1, **f), terms2=torch.empty(Bt, 7, **f),
+                terms=torch.empty(Bt, 1, 5, **f), tstatus=torch.zeros(Bt, **i), Gc=torch.empty(Bt, 6, 3, **f),
+                hc=torch.empty(Bt, 6, **f), cstatus=torch.zeros(Bt, 1, **i), P=torch.empty(Bt, 3, 3, **f),
+                q=torch.empty(Bt, 3, **f), y=torch.empty(Bt, 3, **f), sstatus=torch.zeros(Bt, **i),
+                iters=torch.zeros(Bt, **i), u=torch.empty(Bt, 1, **f), status=torch.zeros(Bt, **i))
+
+
+def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 10.0, 1.0), dt=0.002,
+                                  theta_c=math.pi / 4, delta_c=math.pi / 8, k_alpha=(1.0, 3.0), x_goal=(0.0, 0.0),
+                                  Q_goal=((1.0, 0.0), (0.0, 1.0)), R=1.0, u_ref=None, max_unsafe_prob=0.01, ctrl_reg=1.0,
+                                  relax_weight=100.0, hessian_mode="reference", max_iters=100, stats=None, stream=None):
+    """Bind every argument of `bcbf_pendulum_control_step_f64` once and return `step(ev_start=None, ev_stop=None)`.
+
+    gp: dict(Lop, Vw, X, UHB, ell, s2, Bm, M0, A[, kernel]) of a learned model -- a leading axis of 1 on the GP tensors is
+    one model shared by every instance (regime S), Bt one model per instance (regime I) -- or None for the no-GP mode
+    (the mean model is the whole model; ControlCBFCLFGroundTruth).  mean_model: None (ZeroDynamicsModel) or the pendulum
+    (mass, gravity, length) added to the learned mean; true_model: the plant's (mass, gravity, length).  The defaults are
+    those of ControlPendulumCBFLearned / run_pendulum_control_online_learning (pendulum.py:909-1048).  u_ref: a [Bt,1]
+    tensor read at every step instead of the greedy nominal control.  stats = (min_h[Bt], fails[Bt] int32), updated in
+    place.  x[Bt,2] (fp64) advances in place by dt at every step; the tensors must keep their storage."""
+    from .cbc2 import cbc2_safety_factor
+    Bt = x.shape[0]
+    f = dict(dtype=x.dtype, device=x.device)
+    if x.dtype != torch.float64:
+        raise TypeError("the pendulum control step is fp64")
+    if gp is None:                 # no learned model: s2 = 0 removes every variance term of the rel-degree-2 terms
+        gp = dict(Lop=None, Vw=None, X=None, UHB=None, M0=None, ell=torch.ones(Bt, 2, **f), s2=torch.zeros(Bt, **f),
+                  Bm=torch.eye(2, **f).expand(Bt, 2, 2).contiguous(), A=torch.eye(2, **f).expand(Bt, 2, 2).contiguous())
+        N, shared, kernel = 0, 0, "rbf"
+    else:
+        _chk(x, gp["Lop"], gp["Vw"], gp["X"], gp["UHB"], gp["M0"])
+        N = gp["X"].shape[1]
+        shared = 1 if gp["X"].shape[0] == 1 else 0
+        if not shared and gp["X"].shape[0] != Bt:
+            raise ValueError("GP tensors must carry a leading axis of 1 (shared model) or Bt")
+        kernel = gp.get("kernel", "rbf")
+        if kernel not in DATA_KERNELS:
+            raise ValueError("gp['kernel'] must be one of %s" % (DATA_KERNELS,))
+        gp = dict(gp)
+        for k in ("ell", "s2", "Bm", "A"):                   # the terms kernel reads these per instance
+            v = gp[k]
+            if v.shape[0] != Bt:
+                gp[k] = v.expand(Bt, *v.shape[1:]).contiguous()
+    _chk(x, gp["ell"], gp["s2"], gp["Bm"], gp["A"], ws["Mk"], ws["y"], u_ref)
+    kalpha = torch.tensor(k_alpha, **f)
+    xg = (ctypes.c_double * 2)(*[float(v) for v in x_goal])
+    Qg = (ctypes.c_double * 4)(*[float(v) for row in Q_goal for v in row])
+    mm = (0, 1.0, 1.0, 1.0) if mean_model is None else (1,) + tuple(float(v) for v in mean_model)
+    min_h, fails = stats if stats is not None else (None, None)
+    if stats is not None:
+        _chk(x, min_h, fails)
+    head = (_p(gp["Lop"]), _p(gp["Vw"]), _p(gp["X"]), _p(gp["UHB"]), _p(gp["ell"]), _p(gp["s2"]), _p(gp["Bm"]),
+            _p(gp["M0"]), _p(gp["A"]), N, shared, DATA_KERNELS.index(kernel), mm[0], mm[1], mm[2], mm[3], float(theta_c),
+            float(delta_c), _p(kalpha), xg, Qg, float(R), _p(u_ref), cbc2_safety_factor(max_unsafe_prob), float(ctrl_reg),
+            float(relax_weight), HESSIAN_MODES[hessian_mode], int(max_iters), float(true_model[0]), float(true_model[1]),
+            float(true_model[2]), float(dt), _p(x)) + tuple(
+        _p(ws[k]) for k in ("Mk", "Bk", "G", "Mj", "h", "gh", "Hh", "u_ref", "terms2", "terms", "tstatus", "Gc", "hc",
+                            "cstatus", "P", "q", "y", "sstatus", "iters", "u", "status")) + (_p(min_h), _p(fails), Bt, 2, 1)
+    keep = (gp, dict(ws), x, kalpha, xg, Qg, u_ref, stats, stream)      # the pointers above live as long as these
+    fn, dev, out = lib.bcbf_pendulum_control_step_f64, x.device, ws["u"]
+    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+
+    def step(ev_start=None, ev_stop=None):
+        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
+        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
+        rc = fn(*head, ev0, ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            check(rc, "bcbf_pendulum_control_step")
+        return out
+    step.keep = keep
+    return step
+
+
+def pendulum_control_step(gp, ws, x, **kw):
+    """One control step of the pendulum safety filter for a batch (see `pendulum_control_step_prepare`); returns ws['u']."""
+    return pendulum_control_step_prepare(gp, ws, x, **kw)()

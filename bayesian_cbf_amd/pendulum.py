@@ -382,3 +382,27 @@ def speed_test_matrix_vector(logger_class=None, **kw):
     events_file = _newest_events_file(logger.experiment_logs_dir)
     speed_test_matrix_vector_vis(events_file)
     return events_file
+
+
+# ------------------------------------------------------------------------------------------------
+# The safety filter of ControlPendulumCBFLearned (pendulum.py:909-961) run as a batch of closed loops: upstream's own
+# learned pendulum controller cannot be constructed (ControlCBFLearned calls clf_class=None), so the working definition is
+# SOCPController(cbfs=[RadialCBFRelDegree2], clf=None) with the greedy nominal controller (bcbf_pendulum_control_step).
+def pendulum_bayes_cbf_safe_rollouts(Bt=4096, numSteps=250, D=400, max_train=200, training_iter=50, theta0=7 * math.pi / 12,
+                                     omega0=-0.01, tau=0.01, mass=1, gravity=10, length=1, seed=0, device="cuda", **kw):
+    """Fit a ControlAffineRegressor on one randomised pendulum trajectory (`sampling_pendulum_data` under ControlRandom, a
+    random subset of `max_train` rows, `training_iter` Adam steps: learn_dynamics_from_data, pendulum.py:345-371), then run
+    `rollouts.pendulum_safety_rollouts` with that ONE model shared by all Bt instances (regime S).  Returns
+    (regressor, rollout result)."""
+    from .control_affine_model import ControlAffineRegressor
+    from .rollouts import pendulum_safety_rollouts
+    torch.manual_seed(seed)
+    pend_env = PendulumDynamicsModel(m=1, n=2, mass=mass, gravity=gravity, length=length)
+    dX, X, U = sampling_pendulum_data(pend_env, D=D, x0=torch.tensor([theta0, omega0]), dt=tau,
+                                      controller=ControlRandom(mass=mass, gravity=gravity, length=length).control)
+    dgp, _ = learn_dynamics_from_data(dX, X, U, pend_env, ControlAffineRegressor, None, max_train=max_train,
+                                      training_iter=training_iter, device=device, dtype=torch.float64)
+    gp = dict(dgp._state(), kernel=getattr(dgp, "data_kernel", "rbf"))
+    kw.setdefault("true_model", (mass, gravity, length))
+    return dgp, pendulum_safety_rollouts(Bt, numSteps=numSteps, gp=gp, shared=True, theta0=theta0, omega0=omega0,
+                                         device=device, seed=seed, **kw)

@@ -8,6 +8,7 @@ every trajectory at once, sharded over GPUs by `distributed.shard_range`, statis
 at the end."""
 import math
 import os
+import time
 
 import torch
 
@@ -1011,3 +1012,69 @@ def final_model_vs_fp64_refit(final, sample=64):
             dB = ((f64(Bk_all[lo:hi][idx]) - Br).abs().amax(dim=(1, 2)) / prior)[ok].max()
             worst["Mk"], worst["Bk"] = max(worst["Mk"], float(dM)), max(worst["Bk"], float(dB))
     return worst
+
+
+def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12, omega0=-0.01, start_noise=0.05,
+                             gp=None, shared=False, mean_model=None, true_model=(1.0, 10.0, 1.0), max_unsafe_prob=0.01,
+                             k_alpha=(1.0, 3.0), cbf_col_theta=math.pi / 4, cbf_col_delta=math.pi / 8,
+                             dtype=torch.float64, device="cuda", use_graph=False, record=False, seed=0, max_iters=100,
+                             hessian_mode="reference"):
+    """Bt closed loops of the pendulum's rel-degree-2 safety filter (SOCPController with cbfs = [RadialCBFRelDegree2] and
+    the greedy nominal controller, bcbf_pendulum_control_step) from perturbed start states, numSteps steps each.  The
+    defaults are run_pendulum_control_online_learning's (pendulum.py:1041-1048: theta0 = 7 pi/12, tau = 0.002, 250 steps,
+    float64) with the barrier of RadialCBFRelDegree2 (:643-661).
+
+    gp: None (no-GP mode: the mean model is the whole model, ControlCBFCLFGroundTruth) or the state dict of a learned model
+    (`ControlAffineRegressor.gp_dict()` layout: Lop, Vw, X, UHB, ell, s2, Bm, M0, A[, kernel]); shared=True queries ONE
+    model (instance 0 of gp, regime S) from every instance, otherwise gp carries Bt models (regime I).
+    mean_model: None or the pendulum (mass, gravity, length) added to the learned mean.  A trajectory collides when
+    min_h < 0 (NaN-safe: anything not provably >= 0 counts).  Statistics go through `reduce_rollout_stats` (one
+    collective at the end, as C4); use_graph replays one captured step on one stream.  Returns dict(stats, x_final[Bt,2],
+    min_h[Bt], fails[Bt], traj[numSteps+1,Bt,2] (record), u[numSteps,Bt] (record), loop_seconds)."""
+    dev = torch.device(device)
+    f = dict(dtype=dtype, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    x0 = torch.tensor([theta0, omega0], **f)
+    x = (x0 + start_noise * torch.randn(Bt, 2, generator=gen, **f)).contiguous()
+    if gp is not None and shared:
+        gp = {k: (v[:1].contiguous() if torch.is_tensor(v) and k in ("Lop", "Vw", "X", "UHB", "M0") else v)
+              for k, v in gp.items()}
+    ws = ops.pendulum_workspace(Bt, dtype, dev)
+    min_h = torch.full((Bt,), float("inf"), **f)
+    fails = torch.zeros(Bt, dtype=torch.int32, device=dev)
+    step = ops.pendulum_control_step_prepare(gp, ws, x, mean_model=mean_model, true_model=true_model, dt=dt,
+                                             theta_c=cbf_col_theta, delta_c=cbf_col_delta, k_alpha=k_alpha,
+                                             max_unsafe_prob=max_unsafe_prob, max_iters=max_iters,
+                                             hessian_mode=hessian_mode, stats=(min_h, fails))
+    traj = torch.empty(numSteps + 1, Bt, 2, **f) if record else None
+    us = torch.empty(numSteps, Bt, **f) if record else None
+    if record:
+        traj[0] = x
+    torch.cuda.synchronize(dev)
+    graph = None
+    if use_graph and not record:
+        side = torch.cuda.Stream(device=dev)
+        saved = [v.clone() for v in (x, min_h, fails)]
+        with torch.cuda.stream(side):                   # warm-up on the capture stream
+            step()
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            step()
+        for dst, src in zip((x, min_h, fails), saved):      # the warm-up advanced the state: restore it
+            dst.copy_(src)
+        torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter()
+    for t in range(numSteps):
+        if graph is not None:
+            graph.replay()
+        else:
+            step()
+        if record:
+            traj[t + 1] = x
+            us[t] = ws["u"][:, 0]
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter() - t_loop
+    collided = ~(min_h >= 0)
+    stats = reduce_rollout_stats(collided.sum(), min_h.min(), 0.0, (fails > 0).sum(), Bt)
+    return dict(stats=stats, x_final=x, min_h=min_h, fails=fails, traj=traj, u=us, loop_seconds=t_loop, ws=ws)

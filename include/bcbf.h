@@ -806,6 +806,65 @@ int bcbf_unicycle_control_step_observe_f64(
     double* Bk, double* cones, int* cstatus, double* y, int* status, int* iters, double dt, double L_true, int Bt,
     int N, int Kob, int max_iters, int shared_gp, const double* xq, double* obs_x, double* obs_uh, double* obs_y,
     int obs_ld, double* xq_next, int flags, void* ev_start, void* ev_stop, void* stream);
+
+/* ---- The pendulum's rel-degree-2 safety loop (SOCPController with cbfs = [RadialCBFRelDegree2], clf = None and the
+ * greedy nominal controller: controllers.py:569-591, pendulum.py:643-746), batched: n = 2, m = 1.
+ *
+ * Explicit-Euler plant step of the true pendulum, x += (f(x) + g(x) u) dt with f = [omega, -(g/l) sin theta],
+ * g = [0, 1/(m l)]', then theta <- ((theta + pi) mod 2 pi) - pi (floored modulo): PendulumDynamicsModel.step
+ * (sampling_pendulum, pendulum.py:164-233).  x[Bt,2] in place, u[Bt,1]. */
+int bcbf_pendulum_plant_step_f32(float* x, const float* u, float mass, float gravity, float length, float dt, int Bt,
+                                 void* stream);
+int bcbf_pendulum_plant_step_f64(double* x, const double* u, double mass, double gravity, double length, double dt,
+                                 int Bt, void* stream);
+
+/* Per-instance status of bcbf_pendulum_control_step (status[Bt]); the instance is driven with u = u_ref unless 0:
+ *   0 (BCBF_SOCP_OPTIMAL), 1 (BCBF_SOCP_MAXITER), 2 (BCBF_SOCP_DIVERGED): bcbf_coneqp_f64's status of the program;
+ *   3 (BCBF_SOCP_BADCONE): a cone row could not be factored, as SOCPController.control reports it (the kind-1 safety
+ *     cone has an eigen fallback, so this step does not produce it today);
+ *   BCBF_PENDULUM_BADHESSIAN: the kernel Hessian of L_f h has an eigenvalue <= -2e-3 (bcbf_cbc2_terms status 1), where
+ *     the host path raises AssertionError (gp_algebra.py:386); takes precedence over the others. */
+#define BCBF_PENDULUM_BADHESSIAN 5
+
+/* One control step of the pendulum safety filter for Bt instances, enqueued on `stream` in one host call with no host
+ * synchronisation and no allocation:
+ *   1. bcbf_posterior_jets{,_matern52,_rbfm52}_f64 (kernel_kind 0/1/2) at x -- skipped when Lop == NULL;
+ *   2. task kernel: Mk += [fhat | ghat], Mj[:, :, (1+i) C] += d fhat / d x_i of the deterministic mean model (a pendulum
+ *      (mean_mass, mean_gravity, mean_length) when mean_model != 0; none = ZeroDynamicsModel), exactly as
+ *      cbc2.reldeg2_quadratic_terms does; h = cos(delta_c) - cos(theta - theta_c), gh, Hh; u_ref = the caller's
+ *      u_ref_in[Bt,1] or, when u_ref_in == NULL, GreedyController (x_goal[2], Q_goal[2,2] row-major and R: HOST
+ *      values; lambda = 1/2; this dt) on the shifted posterior mean; P = 0, q = e_0;
+ *   3. bcbf_cbc2_terms_f64 (kalpha[2] device, hessian_mode, kernel_kind) linearised at u_ref -> terms2[Bt,7], tstatus;
+ *      terms[Bt,5] = its first five entries;
+ *   4. bcbf_controller_cones_f64: objective cone (ctrl_reg, relax_weight) and the kind-1 safety cone scaled by
+ *      safety_factor (cbc2_safety_factor(max_unsafe_prob)), extravars = 2 -> Gc[Bt,6,3], hc[Bt,6], cstatus[Bt];
+ *   5. bcbf_coneqp_f64 (P, q, Gc, hc; cones Q^3 x Q^3; max_iters) -> y[Bt,3] = [y_1, rho, u], sstatus, iters;
+ *   6. plant kernel: u[Bt] = y[:, 2] where status == 0, u_ref elsewhere; status (codes above); when min_h / fails are
+ *      given (both or neither): min_h = min(min_h, h(x_t)) (a non-finite h counts as -inf), fails += (status != 0);
+ *      then x advances as bcbf_pendulum_plant_step (true_mass, true_gravity, true_length, dt).
+ * GP (Lop != NULL): Lop, Vw, X, UHB, M0 per instance, or instance 0 only when shared = 1 (regime S: one model, Bt
+ * queries); ell[Bt,2], s2[Bt], Bm[Bt,2,2], A[Bt,2,2] are per instance in both regimes (the jets read instance 0 of
+ * them when shared) because bcbf_cbc2_terms reads them per instance.
+ * No GP (Lop == NULL, ControlCBFCLFGroundTruth: the mean model is the whole model): the task kernel writes Mk, Mj from
+ * the mean model alone and zeroes Bk, G; pass s2 = 0 (and finite ell, Bm, A): every variance term of bcbf_cbc2_terms is
+ * then exactly 0 and (mean_A, mean_b) = (-A(x), b(x)) of RadialCBFRelDegree2 (pendulum.py:713-746).
+ * Workspaces (all required, device, caller-owned): Mk[Bt,2,2], Bk[Bt,2,2], G[Bt,6,6], Mj[Bt,2,6], h[Bt], gh[Bt,2],
+ * Hh[Bt,2,2], u_ref[Bt], terms2[Bt,7], terms[Bt,5], tstatus[Bt], Gc, hc, cstatus[Bt], P[Bt,3,3], q[Bt,3], y[Bt,3],
+ * sstatus[Bt], iters[Bt] (may be NULL), u[Bt], status[Bt].  ev_start / ev_stop (optional hipEvent_t) bracket the jets.
+ * BCBF_EINVAL, before any HIP call, for: n != 2, m != 1, a null required buffer, an incomplete GP, shared not 0/1,
+ * kernel_kind not 0..2, hessian_mode not 0/1, max_iters < 1, dt <= 0, R <= 0, ctrl_reg or relax_weight <= 0,
+ * safety_factor < 0, a pendulum model with m l == 0.  fp64 only (the reference runs this demo in float64). */
+int bcbf_pendulum_control_step_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
 /* The same control step on a model learned with the opt-in Matern-5/2 data kernel (bcbf_refit_matern52 /
  * bcbf_gp_append_matern52 states): identical arguments; the posterior launch evaluates the Matern kernel (one GP per
  * instance: the streaming kernel; shared_gp: the matrix-core query bcbf_posterior_shared_matern52), the fused task rows /

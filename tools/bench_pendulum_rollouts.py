@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""The pendulum's rel-degree-2 safety loop (bcbf_pendulum_control_step_f64: jets -> task rows -> cbc2 terms -> cones ->
+coneqp -> plant step), fp64, N = 512 training points, 250 closed-loop steps per configuration: regime S (one model
+queried by every instance) at Bt = 4096 and 32768, regime I (one model per instance) at Bt = 4096.  One JSON line per
+configuration: instance-steps/s of the eager loop (one host call per step) and of the HIP-graph replay, and the share of
+the step the jets launch takes (events around it, eager loop)."""
+import json
+import math
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from bayesian_cbf_amd import ops
+from bayesian_cbf_amd.rollouts import pendulum_safety_rollouts
+from bayesian_cbf_amd.synthetic import make_instances
+
+
+def model(n_models, N):
+    """Models of the pendulum itself: training states over theta in [-3, 3], omega in [-pi, pi], targets the true
+    dynamics [omega, -10 sin theta + u] (mass 1, gravity 10, length 1), zero prior mean; the hyper-parameters are
+    make_instances' (a throughput benchmark: the model must be good enough that the programs are solvable)."""
+    p = make_instances(n_models, N, 2, 1, dtype=torch.float64, device="cuda", seed=3)
+    X = p["X"]
+    X[..., 0] = (X[..., 0] + 1.5) * 2.0
+    th, om, u = X[..., 0], X[..., 1], p["UH"][..., 1]
+    p["Xdot"] = torch.stack([om, -10.0 * torch.sin(th) + u], dim=-1).contiguous()
+    Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])
+    assert (info == 0).all()
+    Vw, _ = ops.potrs(Lop, p["Xdot"], p["UH"], p["M0"], want_alpha=False)
+    return dict(Lop=Lop, Vw=Vw, X=p["X"], UHB=UHB, ell=p["ell"], s2=p["s2"], Bm=p["Bm"], M0=p["M0"], A=p["A"])
+
+
+def jets_share(gp, Bt, steps=50):
+    """Fraction of the eager step spent in the jets launch (hipEvents around it, recorded by the entry point)."""
+    x = torch.zeros(Bt, 2, dtype=torch.float64, device="cuda")
+    x[:, 0] = 7 * math.pi / 12
+    ws = ops.pendulum_workspace(Bt, torch.float64, "cuda")
+    step = ops.pendulum_control_step_prepare(gp, ws, x)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for a, b in evs:                 # torch creates the HIP event at its first record; the library records it afterwards
+        a.record()
+        b.record()
+    for _ in range(10):
+        step()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for a, b in evs:
+        step(a, b)
+    e1.record()
+    torch.cuda.synchronize()
+    jets = sum(a.elapsed_time(b) for a, b in evs)
+    return jets / e0.elapsed_time(e1), jets / steps
+
+
+def main(configs=(("S", 4096), ("S", 32768), ("I", 4096))):
+    N, steps = 512, int(os.environ.get("BCBF_PEND_STEPS", "250"))
+    for regime, Bt in configs:
+        gp = model(1 if regime == "S" else Bt, N)
+        kw = dict(numSteps=steps, gp=gp, shared=regime == "S")
+        pendulum_safety_rollouts(Bt, **dict(kw, numSteps=20))                     # warm-up (clocks, lazy loads)
+        eager = pendulum_safety_rollouts(Bt, **kw)
+        graph = pendulum_safety_rollouts(Bt, use_graph=True, **kw)
+        share, jets_ms = jets_share(gp, Bt)
+        print(json.dumps(dict(regime=regime, Bt=Bt, N=N, dtype="float64", steps=steps,
+                              eager_instance_steps_per_s=Bt * steps / eager["loop_seconds"],
+                              graph_instance_steps_per_s=Bt * steps / graph["loop_seconds"],
+                              eager_ms_per_step=eager["loop_seconds"] * 1e3 / steps,
+                              graph_ms_per_step=graph["loop_seconds"] * 1e3 / steps,
+                              jets_share=share, jets_ms=jets_ms, collisions=eager["stats"]["collisions"],
+                              instances_with_failed_programs=eager["stats"]["solver_failures"], min_h=eager["stats"]["min_h"],
+                              graph_equals_eager=bool(torch.equal(eager["x_final"], graph["x_final"])))), flush=True)
+        del gp, eager, graph
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    # --only S:4096 (repeatable): a subset of the configurations (profiling runs)
+    only = [a.split(":") for a in sys.argv[sys.argv.index("--only") + 1:]] if "--only" in sys.argv else None
+    main(tuple((r, int(b)) for r, b in only) if only else ((("S", 4096), ("S", 32768), ("I", 4096))))
