@@ -35,6 +35,11 @@ _SIGS = {
     "bcbf_pendulum_control_step_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
                                                ctypes.POINTER(c_double), c_double, P] + [c_double] * 3 + [c_int] * 2
                                        + [c_double] * 4 + [P] * 24 + [c_int] * 3 + [P] * 3),
+    "bcbf_pendulum_control_step_observe_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
+                                                       ctypes.POINTER(c_double), c_double, P] + [c_double] * 3
+                                               + [c_int] * 2 + [c_double] * 4 + [P] * 24
+                                               + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
+                                               + [c_int] * 3 + [P] * 3),
 }
 _TSIGS = {
     "bcbf_kb_build": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],

@@ -11,6 +11,10 @@
 // Plant kernel: u = y[2:] where the program was solved, u_ref elsewhere (SOCPController.control on a batch); the safety
 // bookkeeping (min_h over h(x_t) before the step, failed programs); x += (f + g u) dt on the true pendulum with the theta
 // wrap of PendulumDynamicsModel.step.
+// The observing entry (bcbf_pendulum_control_step_observe_f64) instantiates both kernels with Learn = true: the task
+// kernel can write the GP prior of a regressor with no data and wraps the greedy u_ref in the epsilon-greedy explorer
+// (EpsilonGreedyController, controllers.py:269-285); the plant kernel writes the step's observation row
+// (MeanAdjustedModel.train, controllers.py:320-378).  The Learn = false instantiations are the plain entry's.
 #include "bcbf_common.h"
 
 namespace bcbf {
@@ -21,6 +25,21 @@ struct PendulumParams {
     T mean_mass, mean_gravity, mean_length;     // deterministic mean model (has_mean)
     T theta_c, delta_c;                         // RadialCBFRelDegree2: cbf_col_theta, cbf_col_delta
     T xg[2], Qg[4], R, dt;                      // GreedyController: x_goal, Q (x_quad_goal_cost), R (u_quad_cost), dt
+};
+
+// What the observing entry adds (read only by the Learn = true instantiations)
+template <typename T>
+struct PendulumLearn {
+    int prior;                                  // no GP: write the prior of a regressor with no data (needs M0, s2, Bm)
+    const T *M0, *s2, *Bm;                      // M0[Bt,C,n], s2[Bt], Bm[Bt,C,C]
+    const T* explore;                           // [Bt,2] uniform draws (coin, action) or NULL
+    T eps;                                      // exploration probability of this step
+    int clip;                                   // clip u_ref to [lo, hi]
+    T lo, hi;
+    T *obs_x, *obs_uh, *obs_y;                  // observation row at b * obs_ld (all three or none)
+    int obs_ld;
+    int has_mean;                               // the mean model the targets subtract (as PendulumParams)
+    T mean_mass, mean_gravity, mean_length;
 };
 
 // x <- x + (f(x) + g(x) u) dt,  theta wrapped to [-pi, pi) as ((theta + pi) % 2 pi) - pi with Python's (floored) modulo
@@ -36,19 +55,27 @@ __device__ inline void pendulum_euler(T& th, T& om, T u, T mass, T gravity, T le
     th = r - T(M_PI);
 }
 
-template <typename T>
+template <typename T, bool Learn>
 __global__ void __launch_bounds__(256)
 pendulum_task_kernel(const T* __restrict__ x, T* __restrict__ Mk, T* __restrict__ Bk, T* __restrict__ G,
                      T* __restrict__ Mj, T* __restrict__ h, T* __restrict__ gh, T* __restrict__ Hh,
                      const T* __restrict__ u_ref_in, T* __restrict__ u_ref, double* __restrict__ P,
-                     double* __restrict__ q, PendulumParams<T> p, int Bt) {
+                     double* __restrict__ q, PendulumParams<T> p, PendulumLearn<T> L, int Bt) {
     constexpr int n = 2, C = 2, CT = C * (1 + n);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= Bt) return;
     const T th = x[b * n], om = x[b * n + 1];
     T* mk = Mk + (size_t)b * n * C;
     T* mj = Mj + (size_t)b * n * CT;
-    if (!p.has_gp) {              // no learned model: the mean model is the whole model, every variance term is 0
+    if (Learn && !p.has_gp && L.prior) {
+        // a regressor with no data (cbc2.posterior_for, control_affine_model.py:495-506): Mk = M0', Bk = s2 Bm, G = Mj = 0
+        const T* m0 = L.M0 + (size_t)b * C * n;
+        for (int i = 0; i < n; ++i)
+            for (int c = 0; c < C; ++c) mk[i * C + c] = m0[c * n + i];
+        for (int i = 0; i < n * CT; ++i) mj[i] = T(0);
+        for (int i = 0; i < C * C; ++i) Bk[(size_t)b * C * C + i] = L.s2[b] * L.Bm[(size_t)b * C * C + i];
+        for (int i = 0; i < CT * CT; ++i) G[(size_t)b * CT * CT + i] = T(0);
+    } else if (!p.has_gp) {       // no learned model: the mean model is the whole model, every variance term is 0
         for (int i = 0; i < n * C; ++i) mk[i] = T(0);
         for (int i = 0; i < n * CT; ++i) mj[i] = T(0);
         for (int i = 0; i < C * C; ++i) Bk[(size_t)b * C * C + i] = T(0);
@@ -82,6 +109,15 @@ pendulum_task_kernel(const T* __restrict__ x, T* __restrict__ Mk, T* __restrict_
         const T cc = (T(1) - lam) * (g0 * (p.Qg[0] * r0 + p.Qg[1] * r1) + g1 * (p.Qg[2] * r0 + p.Qg[3] * r1));
         u0 = cc / Q;
     }
+    if constexpr (Learn) {
+        // EpsilonGreedyController: the uniform action lo + a (hi - lo) when the coin falls below eps, then
+        // clip = max(min(u, hi), lo) (misc.py:287-288; a NaN stays NaN, as torch.min / torch.max keep it)
+        if (L.explore && L.explore[(size_t)b * 2] < L.eps) u0 = L.lo + L.explore[(size_t)b * 2 + 1] * (L.hi - L.lo);
+        if (L.clip) {
+            u0 = u0 > L.hi ? L.hi : u0;
+            u0 = u0 < L.lo ? L.lo : u0;
+        }
+    }
     u_ref[b] = u0;
     for (int i = 0; i < 9; ++i) P[(size_t)b * 9 + i] = 0.0;                  // min y_1: P = 0, q = e_0 (controllers.py:575)
     q[(size_t)b * 3] = 1.0;
@@ -96,12 +132,12 @@ __global__ void __launch_bounds__(256) pendulum_pack_terms_kernel(const T* __res
     for (int i = 0; i < 5; ++i) t[(size_t)b * 5 + i] = t2[(size_t)b * 7 + i];
 }
 
-template <typename T>
+template <typename T, bool Learn>
 __global__ void __launch_bounds__(256)
 pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int* __restrict__ sstatus,
                       const int* __restrict__ cstatus, const int* __restrict__ tstatus, const T* __restrict__ u_ref,
                       const T* __restrict__ h, T* __restrict__ u, int* __restrict__ status, T* __restrict__ min_h,
-                      int* __restrict__ fails, T mass, T gravity, T length, T dt, int Bt) {
+                      int* __restrict__ fails, T mass, T gravity, T length, T dt, PendulumLearn<T> L, int Bt) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= Bt) return;
     const int st = tstatus[b] == 1 ? BCBF_PENDULUM_BADHESSIAN : cstatus[b] != 0 ? BCBF_SOCP_BADCONE : sstatus[b];
@@ -116,6 +152,25 @@ pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int
     }
     T th = x[b * 2], om = x[b * 2 + 1];
     pendulum_euler<T>(th, om, ub, mass, gravity, length, dt);
+    if constexpr (Learn) {
+        // the buffered row (MeanAdjustedModel._train): X = x_t, UH = (1, u_t), Y = (x_{t+1} - x_t) / dt - (f + g u)(x_t) of
+        // the mean model, from the STORED states -- theta_{t+1} is wrapped, so a step across +-pi gives a target ~ 2 pi / dt
+        if (L.obs_x) {
+            const T t0 = x[b * 2], w0 = x[b * 2 + 1];
+            T m0 = T(0), m1 = T(0);
+            if (L.has_mean) {
+                m0 = w0 + T(0) * ub;
+                m1 = -(L.mean_gravity / L.mean_length) * sin(t0) + T(1) / (L.mean_mass * L.mean_length) * ub;
+            }
+            const size_t r = (size_t)b * L.obs_ld * 2;
+            L.obs_x[r] = t0;
+            L.obs_x[r + 1] = w0;
+            L.obs_uh[r] = T(1);
+            L.obs_uh[r + 1] = ub;
+            L.obs_y[r] = (th - t0) / dt - m0;
+            L.obs_y[r + 1] = (om - w0) / dt - m1;
+        }
+    }
     x[b * 2] = th;
     x[b * 2 + 1] = om;
 }
@@ -134,6 +189,96 @@ pendulum_plant_step_kernel(T* __restrict__ x, const T* __restrict__ u, T mass, T
 static int pendulum_einval(const char* why) {
     set_error_message(why);
     return BCBF_EINVAL;
+}
+
+template <bool Learn>
+static int pendulum_control_step(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    const PendulumLearn<double>& L, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
+    // ---- argument checks, before any HIP call
+    if (Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
+    if (n != 2 || m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
+    if (!x || !ell || !s2 || !Bm || !A || !kalpha || !x_goal || !Q_goal)
+        return pendulum_einval("pendulum_control_step: null state / model / task buffer");
+    if (!Mk || !Bk || !G || !Mj || !h || !gh || !Hh || !u_ref || !terms2 || !terms || !tstatus || !Gc || !hc ||
+        !cstatus || !P || !q || !y || !sstatus || !u || !status)
+        return pendulum_einval("pendulum_control_step: null workspace buffer");
+    if (!min_h != !fails) return pendulum_einval("pendulum_control_step: min_h and fails go together");
+    if (Lop && (!Vw || !X || !UHB || !M0 || N < 1)) return pendulum_einval("pendulum_control_step: incomplete GP");
+    if (shared != 0 && shared != 1) return pendulum_einval("pendulum_control_step: shared must be 0 or 1");
+    if (kernel_kind < 0 || kernel_kind >= BCBF_KINDS) return pendulum_einval("pendulum_control_step: bad kernel_kind");
+    if (hessian_mode != 0 && hessian_mode != 1) return pendulum_einval("pendulum_control_step: bad hessian_mode");
+    if (max_iters < 1) return pendulum_einval("pendulum_control_step: max_iters < 1");
+    if (!(dt > 0.0) || !(R > 0.0)) return pendulum_einval("pendulum_control_step: dt and R must be > 0");
+    if (mean_model && !(mean_mass * mean_length != 0.0)) return pendulum_einval("pendulum_control_step: mean model m l == 0");
+    if (!(true_mass * true_length != 0.0)) return pendulum_einval("pendulum_control_step: true model m l == 0");
+    if (!(safety_factor >= 0.0) || !(ctrl_reg > 0.0) || !(relax_weight > 0.0))
+        return pendulum_einval("pendulum_control_step: safety factor, ctrl_reg, relax_weight");
+    if (Learn) {
+        if (L.prior != 0 && L.prior != 1) return pendulum_einval("pendulum_control_step_observe: prior must be 0 or 1");
+        if (!Lop && L.prior && (!L.M0 || !L.s2 || !L.Bm))
+            return pendulum_einval("pendulum_control_step_observe: the prior needs M0");
+        if (!(L.eps >= 0.0 && L.eps <= 1.0)) return pendulum_einval("pendulum_control_step_observe: eps must lie in [0, 1]");
+        if (L.explore && !L.clip) return pendulum_einval("pendulum_control_step_observe: explore needs ctrl_range");
+        if (L.explore && u_ref_in) return pendulum_einval("pendulum_control_step_observe: explore wraps the greedy u_ref, not u_ref_in");
+        if (L.clip && !(L.lo <= L.hi)) return pendulum_einval("pendulum_control_step_observe: ctrl_range needs lo <= hi");
+        if ((L.obs_x || L.obs_uh || L.obs_y) && (!L.obs_x || !L.obs_uh || !L.obs_y))
+            return pendulum_einval("pendulum_control_step_observe: obs_x, obs_uh, obs_y go together");
+        if (L.obs_x && L.obs_ld < 1) return pendulum_einval("pendulum_control_step_observe: obs_ld < 1");
+        if (L.has_mean && !(L.mean_mass * L.mean_length != 0.0))
+            return pendulum_einval("pendulum_control_step_observe: mean model m l == 0");
+    }
+    if (Bt == 0) return BCBF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // 1. jets of the learned model at x (skipped without one: the task kernel writes the mean model alone)
+    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+    int rc = BCBF_OK;
+    if (Lop) {
+        auto jets = kernel_kind == 0 ? bcbf_posterior_jets_f64 : kernel_kind == 1 ? bcbf_posterior_jets_matern52_f64
+                                                                                  : bcbf_posterior_jets_rbfm52_f64;
+        rc = jets(Lop, Vw, X, UHB, ell, s2, Bm, M0, x, Mk, Bk, G, Mj, nullptr, shared, Bt, N, 2, 1, stream);
+    }
+    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+    if (rc) return rc;
+    // 2. task kernel
+    PendulumParams<double> p;
+    p.has_gp = Lop != nullptr;
+    p.has_mean = mean_model != 0;
+    p.has_uref = u_ref_in != nullptr;
+    p.mean_mass = mean_mass; p.mean_gravity = mean_gravity; p.mean_length = mean_length;
+    p.theta_c = theta_c; p.delta_c = delta_c;
+    p.xg[0] = x_goal[0]; p.xg[1] = x_goal[1];
+    for (int i = 0; i < 4; ++i) p.Qg[i] = Q_goal[i];
+    p.R = R; p.dt = dt;
+    const dim3 grid((Bt + 255) / 256), block(256);
+    hipLaunchKernelGGL((pendulum_task_kernel<double, Learn>), grid, block, 0, st, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref_in,
+                       u_ref, P, q, p, L, Bt);
+    if ((rc = check_launch("pendulum_task"))) return rc;
+    // 3. rel-degree-2 terms (linearised at u_ref), 4. the program's rows (objective cone + safety cone of kind 1)
+    if ((rc = bcbf_cbc2_terms_f64(Mk, Bk, G, Mj, A, Bm, ell, s2, h, gh, Hh, kalpha, u_ref, terms2, tstatus, Bt, 2, 1,
+                                  hessian_mode, kernel_kind, stream)))
+        return rc;
+    hipLaunchKernelGGL((pendulum_pack_terms_kernel<double>), grid, block, 0, st, terms2, terms, Bt);
+    if ((rc = check_launch("pendulum_pack_terms"))) return rc;
+    const int kind = 1;
+    if ((rc = bcbf_controller_cones_f64(terms, u_ref, &kind, &safety_factor, ctrl_reg, relax_weight, 2, 1, Gc, hc,
+                                        cstatus, Bt, 1, 1, stream)))
+        return rc;
+    // 5. min y_1 over y = [y_1, rho, u] in Q^3 x Q^3
+    const int qdims[2] = {3, 3};
+    if ((rc = bcbf_coneqp_f64(P, q, Gc, hc, 3, 0, qdims, 2, y, sstatus, iters, Bt, max_iters, stream))) return rc;
+    // 6. choose u, bookkeeping, plant step
+    hipLaunchKernelGGL((pendulum_plant_kernel<double, Learn>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
+                       h, u, status, min_h, fails, true_mass, true_gravity, true_length, dt, L, Bt);
+    return check_launch("pendulum_plant");
 }
 
 }  // namespace bcbf
@@ -163,68 +308,41 @@ int bcbf_pendulum_control_step_f64(
     double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
     double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
     int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
-    using bcbf::pendulum_einval;
-    // ---- argument checks, before any HIP call
-    if (Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
-    if (n != 2 || m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
-    if (!x || !ell || !s2 || !Bm || !A || !kalpha || !x_goal || !Q_goal)
-        return pendulum_einval("pendulum_control_step: null state / model / task buffer");
-    if (!Mk || !Bk || !G || !Mj || !h || !gh || !Hh || !u_ref || !terms2 || !terms || !tstatus || !Gc || !hc ||
-        !cstatus || !P || !q || !y || !sstatus || !u || !status)
-        return pendulum_einval("pendulum_control_step: null workspace buffer");
-    if (!min_h != !fails) return pendulum_einval("pendulum_control_step: min_h and fails go together");
-    if (Lop && (!Vw || !X || !UHB || !M0 || N < 1)) return pendulum_einval("pendulum_control_step: incomplete GP");
-    if (shared != 0 && shared != 1) return pendulum_einval("pendulum_control_step: shared must be 0 or 1");
-    if (kernel_kind < 0 || kernel_kind >= bcbf::BCBF_KINDS) return pendulum_einval("pendulum_control_step: bad kernel_kind");
-    if (hessian_mode != 0 && hessian_mode != 1) return pendulum_einval("pendulum_control_step: bad hessian_mode");
-    if (max_iters < 1) return pendulum_einval("pendulum_control_step: max_iters < 1");
-    if (!(dt > 0.0) || !(R > 0.0)) return pendulum_einval("pendulum_control_step: dt and R must be > 0");
-    if (mean_model && !(mean_mass * mean_length != 0.0)) return pendulum_einval("pendulum_control_step: mean model m l == 0");
-    if (!(true_mass * true_length != 0.0)) return pendulum_einval("pendulum_control_step: true model m l == 0");
-    if (!(safety_factor >= 0.0) || !(ctrl_reg > 0.0) || !(relax_weight > 0.0))
-        return pendulum_einval("pendulum_control_step: safety factor, ctrl_reg, relax_weight");
-    if (Bt == 0) return BCBF_OK;
-    hipStream_t st = (hipStream_t)stream;
-    // 1. jets of the learned model at x (skipped without one: the task kernel writes the mean model alone)
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-    int rc = BCBF_OK;
-    if (Lop) {
-        auto jets = kernel_kind == 0 ? bcbf_posterior_jets_f64 : kernel_kind == 1 ? bcbf_posterior_jets_matern52_f64
-                                                                                  : bcbf_posterior_jets_rbfm52_f64;
-        rc = jets(Lop, Vw, X, UHB, ell, s2, Bm, M0, x, Mk, Bk, G, Mj, nullptr, shared, Bt, N, 2, 1, stream);
-    }
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-    if (rc) return rc;
-    // 2. task kernel
-    bcbf::PendulumParams<double> p;
-    p.has_gp = Lop != nullptr;
-    p.has_mean = mean_model != 0;
-    p.has_uref = u_ref_in != nullptr;
-    p.mean_mass = mean_mass; p.mean_gravity = mean_gravity; p.mean_length = mean_length;
-    p.theta_c = theta_c; p.delta_c = delta_c;
-    p.xg[0] = x_goal[0]; p.xg[1] = x_goal[1];
-    for (int i = 0; i < 4; ++i) p.Qg[i] = Q_goal[i];
-    p.R = R; p.dt = dt;
-    const dim3 grid((Bt + 255) / 256), block(256);
-    hipLaunchKernelGGL((bcbf::pendulum_task_kernel<double>), grid, block, 0, st, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref_in,
-                       u_ref, P, q, p, Bt);
-    if ((rc = bcbf::check_launch("pendulum_task"))) return rc;
-    // 3. rel-degree-2 terms (linearised at u_ref), 4. the program's rows (objective cone + safety cone of kind 1)
-    if ((rc = bcbf_cbc2_terms_f64(Mk, Bk, G, Mj, A, Bm, ell, s2, h, gh, Hh, kalpha, u_ref, terms2, tstatus, Bt, 2, 1,
-                                  hessian_mode, kernel_kind, stream)))
-        return rc;
-    hipLaunchKernelGGL((bcbf::pendulum_pack_terms_kernel<double>), grid, block, 0, st, terms2, terms, Bt);
-    if ((rc = bcbf::check_launch("pendulum_pack_terms"))) return rc;
-    const int kind = 1;
-    if ((rc = bcbf_controller_cones_f64(terms, u_ref, &kind, &safety_factor, ctrl_reg, relax_weight, 2, 1, Gc, hc,
-                                        cstatus, Bt, 1, 1, stream)))
-        return rc;
-    // 5. min y_1 over y = [y_1, rho, u] in Q^3 x Q^3
-    const int qdims[2] = {3, 3};
-    if ((rc = bcbf_coneqp_f64(P, q, Gc, hc, 3, 0, qdims, 2, y, sstatus, iters, Bt, max_iters, stream))) return rc;
-    // 6. choose u, bookkeeping, plant step
-    hipLaunchKernelGGL((bcbf::pendulum_plant_kernel<double>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
-                       h, u, status, min_h, fails, true_mass, true_gravity, true_length, dt, Bt);
-    return bcbf::check_launch("pendulum_plant");
+    const bcbf::PendulumLearn<double> L{};
+    return bcbf::pendulum_control_step<false>(
+        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
+        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
+        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
+        P, q, y, sstatus, iters, u, status, min_h, fails, L, Bt, n, m, ev_start, ev_stop, stream);
+}
+
+int bcbf_pendulum_control_step_observe_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
+    bcbf::PendulumLearn<double> L{};
+    L.prior = prior;
+    L.M0 = M0; L.s2 = s2; L.Bm = Bm;
+    L.explore = explore;
+    L.eps = eps;
+    L.clip = ctrl_range != nullptr;
+    L.lo = ctrl_range ? ctrl_range[0] : 0.0;
+    L.hi = ctrl_range ? ctrl_range[1] : 0.0;
+    L.obs_x = obs_x; L.obs_uh = obs_uh; L.obs_y = obs_y; L.obs_ld = obs_ld;
+    L.has_mean = mean_model != 0;
+    L.mean_mass = mean_mass; L.mean_gravity = mean_gravity; L.mean_length = mean_length;
+    return bcbf::pendulum_control_step<true>(
+        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
+        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
+        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
+        P, q, y, sstatus, iters, u, status, min_h, fails, L, Bt, n, m, ev_start, ev_stop, stream);
 }
 }

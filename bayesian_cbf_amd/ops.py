@@ -1344,7 +1344,8 @@ def pendulum_workspace(Bt, dtype=torch.float64, device="cuda"):
 def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 10.0, 1.0), dt=0.002,
                                   theta_c=math.pi / 4, delta_c=math.pi / 8, k_alpha=(1.0, 3.0), x_goal=(0.0, 0.0),
                                   Q_goal=((1.0, 0.0), (0.0, 1.0)), R=1.0, u_ref=None, max_unsafe_prob=0.01, ctrl_reg=1.0,
-                                  relax_weight=100.0, hessian_mode="reference", max_iters=100, stats=None, stream=None):
+                                  relax_weight=100.0, hessian_mode="reference", max_iters=100, stats=None, stream=None, *,
+                                  prior=False, explore=None, eps=0.0, ctrl_range=None, observe=False):
     """Bind every argument of `bcbf_pendulum_control_step_f64` once and return `step(ev_start=None, ev_stop=None)`.
 
     gp: dict(Lop, Vw, X, UHB, ell, s2, Bm, M0, A[, kernel]) of a learned model -- a leading axis of 1 on the GP tensors is
@@ -1353,13 +1354,34 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
     (mass, gravity, length) added to the learned mean; true_model: the plant's (mass, gravity, length).  The defaults are
     those of ControlPendulumCBFLearned / run_pendulum_control_online_learning (pendulum.py:909-1048).  u_ref: a [Bt,1]
     tensor read at every step instead of the greedy nominal control.  stats = (min_h[Bt], fails[Bt] int32), updated in
-    place.  x[Bt,2] (fp64) advances in place by dt at every step; the tensors must keep their storage."""
+    place.  x[Bt,2] (fp64) advances in place by dt at every step; the tensors must keep their storage.
+
+    The keyword-only options route the step to `bcbf_pendulum_control_step_observe_f64` (the loop that learns online,
+    ControlPendulumCBFLearned; without any of them the plain entry runs):
+      prior=True: gp is the hyper-parameter dict (ell, s2, Bm, M0, A; leading axis 1 or Bt) of a regressor that holds no
+        data, without Lop -- the learned part is its GP prior (Mk = M0', Bk = s2 Bm, G = Mj = 0, cbc2.posterior_for);
+      explore=[Bt,2] uniform draws (coin, action), eps, ctrl_range=(lo, hi): the epsilon-greedy wrapper around the greedy
+        u_ref (EpsilonGreedyController: the action lo + a (hi - lo) where coin < eps, then clipped to ctrl_range);
+        ctrl_range alone clips;
+      observe=True: the step writes its observation row (x_t, (1, u_t), (x_{t+1} - x_t)/dt - mean) where the call says.
+    With any of them the returned step is `step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None)`: eps and
+    explore replace the bound ones for this call (eps varies per step), obs = (obs_x, obs_uh, obs_y, ld) are [.,2] tensors
+    whose row b * ld is instance b's (ld = 1: [Bt,2] tensors; a column t of [Bt,T,2] stream buffers: ld = T)."""
     from .cbc2 import cbc2_safety_factor
     Bt = x.shape[0]
     f = dict(dtype=x.dtype, device=x.device)
     if x.dtype != torch.float64:
         raise TypeError("the pendulum control step is fp64")
-    if gp is None:                 # no learned model: s2 = 0 removes every variance term of the rel-degree-2 terms
+    learn = bool(prior) or explore is not None or ctrl_range is not None or bool(observe)
+    if prior and (gp is None or gp.get("Lop") is not None):
+        raise ValueError("prior=True takes the hyper-parameters (ell, s2, Bm, M0, A) of a regressor without data, no Lop")
+    if prior:                      # a regressor with no data: its GP prior, with its own hyper-parameters per instance
+        gp = {k: (gp[k] if gp[k].shape[0] == Bt else gp[k].expand(Bt, *gp[k].shape[1:])).contiguous()
+              for k in ("ell", "s2", "Bm", "M0", "A")}
+        _chk(x, gp["M0"])
+        gp.update(Lop=None, Vw=None, X=None, UHB=None)
+        N, shared, kernel = 0, 0, "rbf"
+    elif gp is None:               # no learned model: s2 = 0 removes every variance term of the rel-degree-2 terms
         gp = dict(Lop=None, Vw=None, X=None, UHB=None, M0=None, ell=torch.ones(Bt, 2, **f), s2=torch.zeros(Bt, **f),
                   Bm=torch.eye(2, **f).expand(Bt, 2, 2).contiguous(), A=torch.eye(2, **f).expand(Bt, 2, 2).contiguous())
         N, shared, kernel = 0, 0, "rbf"
@@ -1393,8 +1415,11 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
         _p(ws[k]) for k in ("Mk", "Bk", "G", "Mj", "h", "gh", "Hh", "u_ref", "terms2", "terms", "tstatus", "Gc", "hc",
                             "cstatus", "P", "q", "y", "sstatus", "iters", "u", "status")) + (_p(min_h), _p(fails), Bt, 2, 1)
     keep = (gp, dict(ws), x, kalpha, xg, Qg, u_ref, stats, stream)      # the pointers above live as long as these
-    fn, dev, out = lib.bcbf_pendulum_control_step_f64, x.device, ws["u"]
+    dev, out = x.device, ws["u"]
     fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    if learn:
+        return _pendulum_observe_step(head[:-3], keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref)
+    fn = lib.bcbf_pendulum_control_step_f64
 
     def step(ev_start=None, ev_stop=None):
         ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
@@ -1402,6 +1427,33 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
         rc = fn(*head, ev0, ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc:
             check(rc, "bcbf_pendulum_control_step")
+        return out
+    step.keep = keep
+    return step
+
+
+def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref):
+    """The step of `pendulum_control_step_prepare` on bcbf_pendulum_control_step_observe_f64 (head: the plain entry's
+    arguments up to `fails`)."""
+    if explore is not None and u_ref is not None:
+        raise ValueError("explore wraps the greedy u_ref; it cannot be combined with a caller's u_ref")
+    _chk(x, explore)
+    rng = None if ctrl_range is None else (ctypes.c_double * 2)(*[float(v) for v in ctrl_range])
+    fn, dev, Bt = lib.bcbf_pendulum_control_step_observe_f64, x.device, x.shape[0]
+    bound = dict(eps=float(eps), explore=explore)
+    keep = keep + (rng, explore)
+
+    def step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None):
+        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
+        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
+        ex = bound["explore"] if explore is None else explore
+        if explore is not None:
+            _chk(x, explore)
+        o = (None, None, None, 1) if obs is None else (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
+        rc = fn(*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, Bt, 2, 1, ev0, ev1,
+                fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            check(rc, "bcbf_pendulum_control_step_observe")
         return out
     step.keep = keep
     return step

@@ -406,3 +406,66 @@ def pendulum_bayes_cbf_safe_rollouts(Bt=4096, numSteps=250, D=400, max_train=200
     kw.setdefault("true_model", (mass, gravity, length))
     return dgp, pendulum_safety_rollouts(Bt, numSteps=numSteps, gp=gp, shared=True, theta0=theta0, omega0=omega0,
                                          device=device, seed=seed, **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# The learning controller of run_pendulum_control_online_learning (pendulum.py:909-961, 1041-1048).
+class ControlPendulumCBFLearned:
+    """One-instance façade of upstream's ControlPendulumCBFLearned, same signature: a `ControlCBFLearned` with
+    `controller_class=SOCPController` and `cbfs=[RadialCBFRelDegree2(model)]` (the barrier on the learned regressor, as
+    upstream builds it), the greedy nominal controller inside the epsilon-greedy explorer, the regressor refit every
+    `train_every_n_steps` steps on at most `max_train` rows (`MeanAdjustedModel`, `iterations` Adam steps per refit).
+    Deviations: upstream's class cannot run (its ControlCBFLearned defaults to QPController with clf=None) and never sets
+    `enable_learning`, so as written it never learns; `enable_learning=False` stays the default here, `True` learns.
+    The plotting arguments are accepted and ignored.  `rollouts.pendulum_learning_rollouts` is the batched form."""
+
+    def __init__(self, theta_goal=0., omega_goal=0., quad_goal_cost=((1.0, 0), (0, 1.0)), x_dim=2, u_dim=1, gamma_sr=1,
+                 delta_sr=10, train_every_n_steps=10, mean_dynamics_model_class=None, egreedy_scheme=(1, 0.01),
+                 iterations=100, dt=0.001, max_train=200, gamma_length_scale_prior=(math.pi / 100, math.pi / 100),
+                 constraint_plotter_class=None, true_model=None, plotfile=None, dtype=torch.float64,
+                 use_ground_truth_model=False, numSteps=1000, ctrl_range=(-15., 15.), u_quad_cost=((1.,),),
+                 enable_learning=False, model=None, exploration_controller_class=None, device=None):
+        """mean_dynamics_model_class None = partial(ZeroDynamicsModel, m=1, n=2), upstream's default.  model: the regressor
+        (default a fresh ControlAffineRegressor(x_dim, u_dim, gamma_length_scale_prior=...) in `dtype`);
+        exploration_controller_class: default `EpsilonGreedyController` (tests pass a replaying subclass)."""
+        from .control_affine_model import ControlAffineRegressor
+        from .controllers import ControlCBFLearned, EpsilonGreedyController, SOCPController
+        from .unicycle_move_to_pose import ZeroDynamicsModel
+        if use_ground_truth_model:
+            raise NotImplementedError("use_ground_truth_model: ControlCBFCLFGroundTruth / the no-GP mode of the batched step")
+        if mean_dynamics_model_class is None:
+            mean_dynamics_model_class = lambda: ZeroDynamicsModel(m=u_dim, n=x_dim)
+        if model is None:
+            model = ControlAffineRegressor(x_dim, u_dim, device=device, dtype=dtype,
+                                           gamma_length_scale_prior=gamma_length_scale_prior)
+        self.model, self.true_model = model, true_model
+        self.cbf2 = RadialCBFRelDegree2(self.model, dtype=dtype)
+        self.controller = ControlCBFLearned(
+            x_dim=x_dim, u_dim=u_dim, model=model, train_every_n_steps=train_every_n_steps, dt=dt, ctrl_range=ctrl_range,
+            x_goal=[theta_goal, omega_goal], x_quad_goal_cost=[list(r) for r in quad_goal_cost],
+            u_quad_cost=[list(r) for r in u_quad_cost], numSteps=numSteps, cbfs=[self.cbf2],
+            exploration_controller_class=exploration_controller_class or EpsilonGreedyController,
+            egreedy_scheme=list(egreedy_scheme), enable_learning=enable_learning,
+            mean_dynamics_model_class=mean_dynamics_model_class, max_train=max_train, controller_class=SOCPController,
+            training_iter=iterations)
+        self.net_model = self.controller.net_model
+
+    @property
+    def last_status(self):
+        return self.controller._controller.last_status
+
+    def control(self, xi, t=None):
+        """u for the state xi ([n]: raises on an unsolved program, as upstream; [1, n]: keeps u_ref, status in
+        `last_status`), and the observation handed to the learner."""
+        return self.controller.control(xi, t=t)
+
+
+def pendulum_online_learning_rollouts(Bt=4096, numSteps=250, tau=0.002, theta0=7 * math.pi / 12, omega0=-0.01,
+                                      fit_iters=100, **kw):
+    """run_pendulum_control_online_learning (pendulum.py:1041-1048: 250 steps, tau = 0.002, theta0 = 7 pi / 12, float64)
+    with ControlPendulumCBFLearned's settings (train every 10 steps, max_train 200, egreedy (1, 0.01), ctrl_range (-15,
+    15), `iterations` = 100 Adam steps per refit) and learning ON, for Bt perturbed starts at once
+    (`rollouts.pendulum_learning_rollouts`)."""
+    from .rollouts import pendulum_learning_rollouts
+    return pendulum_learning_rollouts(Bt, numSteps=numSteps, dt=tau, theta0=theta0, omega0=omega0, fit_iters=fit_iters,
+                                      learning=True, **kw)

@@ -1078,3 +1078,208 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
     collided = ~(min_h >= 0)
     stats = reduce_rollout_stats(collided.sum(), min_h.min(), 0.0, (fails > 0).sum(), Bt)
     return dict(stats=stats, x_final=x, min_h=min_h, fails=fails, traj=traj, u=us, loop_seconds=t_loop, ws=ws)
+
+
+def pendulum_learning_schedule(numSteps, train_every=10, max_train=200):
+    """The refits of the pendulum's learning loop as (t, count, with_replacement): MeanAdjustedModel.train /
+    OnlineLearner.observe (controllers.py:336-378) refit after the control of step t when t > 0 and t % train_every == 0, on
+    the count = t - 1 rows the buffer then holds (0 .. t-2: x_t is not in it yet); beyond max_train rows a refit draws
+    max_train of them WITH replacement (torch.randint, :360-362).  A count of 0 refits nothing (_refit_from_scratch)."""
+    out = []
+    for t in range(1, numSteps):
+        if t % train_every == 0 and t - 1 > 0:
+            out.append((t, t - 1, max_train is not None and t - 1 > max_train))
+    return out
+
+
+def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_train=200, fit_iters=0, learning=True,
+                               egreedy=(1.0, 0.01), ctrl_range=(-15.0, 15.0), mean_model=None, hyper=None, retry_levels=3,
+                               seed=0, record=False, draws=None, x0=None, theta0=7 * math.pi / 12, omega0=-0.01,
+                               start_noise=0.05, true_model=(1.0, 10.0, 1.0), max_unsafe_prob=0.01, k_alpha=(1.0, 3.0),
+                               cbf_col_theta=math.pi / 4, cbf_col_delta=math.pi / 8, fit_lr=0.1,
+                               gamma_length_scale_prior=(math.pi / 100, math.pi / 100), max_iters=100,
+                               hessian_mode="reference", device="cuda"):
+    """Bt closed loops of the pendulum that LEARN their dynamics while the safety filter drives them
+    (ControlPendulumCBFLearned, pendulum.py:909-961, through ControlCBFLearned / MeanAdjustedModel, controllers.py:320-378,
+    665-736; the settings of run_pendulum_control_online_learning, pendulum.py:1041-1048), fp64, regime I: every instance
+    learns its own model from its own rows.  Per step, one call of `bcbf_pendulum_control_step_observe_f64`:
+      - the learned part is the GP prior of the start hyper-parameters until the first refit (cbc2.posterior_for), then the
+        instance's own model; mean_model (None = ZeroDynamicsModel, or the pendulum (mass, gravity, length)) is added;
+      - u_ref = EpsilonGreedyController around the greedy control (controllers.py:269-285): eps_t = epsilon(t, {0: egreedy[0],
+        numSteps: egreedy[1]}), the uniform action lo + a (hi - lo) with probability eps_t, clipped to ctrl_range;
+      - the SOCP safety filter (cbfs = [RadialCBFRelDegree2], clf = None) as `pendulum_safety_rollouts`; an unsolved program
+        keeps u_ref;
+      - the row (x_t, (1, u_t), (x_{t+1} - x_t)/dt - mean) goes to column t of [Bt, numSteps, 2] stream buffers.  The states
+        are the stored, theta-wrapped ones (as the reference's buffer holds them): a step across theta = +-pi gives a target
+        of size ~2 pi / dt, as upstream.
+    Refits (`pendulum_learning_schedule`): after the control of step t, on rows 0 .. t-2 (all of them up to max_train, else
+    torch.randint(count, (max_train,)) rows WITH replacement, gathered on the device); jitter = 1e-5 * rand(N) per refit
+    (make_psd), x10 on the failed instances through `ops.refit_with_retries` (the SAME draw scaled, not a fresh one);
+    fit_iters > 0 first runs that many Adam iterations of the marginal likelihood (`BatchedHyperFit`, gamma length-scale
+    prior, lr fit_lr), hyper-parameters carried from refit to refit; fit_iters = 0 keeps the start values.  hyper: the
+    start, a `ControlAffineRegressor(2, 1)` (its values, and its raw parameters for the fit) or dict(ell, s2, Bm, M0, A)
+    with a leading axis of 1 or Bt; default a fresh regressor's.  The model serves
+    from step t+1 on.  learning=False: no refits, the prior all along (upstream's class as written never learns).
+    Deviations from upstream: its class cannot run (QPController with clf=None by default, enable_learning never set); the
+    draws come from the loop's torch generator (start noise, then explore[T,Bt,2], then per refit the subset indices and
+    the jitter rand), not from Python's `random` / torch's global RNG.
+
+    Eager on one stream; allocation at set-up only (two flat factor buffers at lop_elems(max_train), viewed as
+    [Bt, lop_elems(N)], the step re-bound after each refit); no host read of device values between the first and the last
+    step (fit_iters > 0: the batched fit looks at its factorisation status once per iteration).  draws = the `draws` of an
+    earlier record=True run (explore[T,Bt,2], refits[k] = dict(idx [Bt,max_train] | None, jitter [Bt,N] rand; fit_iters > 0:
+    fit_jitter / fit_target, one [Bt,N] / [Bt,N,2] rand per iteration)): replayed
+    instead of drawn (a column slice of them is a sub-batch's).  x0: [Bt,2] start states (default (theta0, omega0) +
+    start_noise randn).
+    Returns dict(stats (`reduce_rollout_stats`), report, x_final, min_h, fails; record: traj[T+1,Bt,2], u[T,Bt],
+    u_ref[T,Bt], status[T,Bt], draws, rows = the stream buffers (X, UH, Y [Bt,T,2]), final = dict(X, UH, Y, jitter [Bt,N,.]
+    of the last refit, hyper, gp = the model the loop ended with))."""
+    from .controllers import epsilon
+    dev = torch.device(device)
+    f = dict(dtype=torch.float64, device=dev)
+    n, C = 2, 2
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    if x0 is None:
+        x = (torch.tensor([theta0, omega0], **f) + start_noise * torch.randn(Bt, 2, generator=gen, **f)).contiguous()
+    else:
+        x = x0.to(**f).clone().contiguous()
+        if x.shape != (Bt, 2):
+            raise ValueError("x0 must be [Bt, 2]")
+    schedule = pendulum_learning_schedule(numSteps, train_every, max_train) if learning else []
+    # ---- the draws, made (or replayed) at set-up: explore, then per refit the subset indices and the jitter rand
+    if draws is None:
+        explore = torch.rand(numSteps, Bt, 2, generator=gen, **f)
+        refit_draws = []
+        for (t, count, wr) in schedule:
+            idx = torch.randint(count, (Bt, max_train), generator=gen, device=dev) if wr else None
+            refit_draws.append(dict(idx=idx, jitter=torch.rand(Bt, min(count, max_train), generator=gen, **f)))
+    else:
+        explore = draws["explore"].to(**f).contiguous()
+        refit_draws = draws["refits"]
+        if explore.shape != (numSteps, Bt, 2) or len(refit_draws) != len(schedule):
+            raise ValueError("draws do not match (numSteps, Bt) or the refit schedule")
+    start = hyper
+    if start is None:
+        from .control_affine_model import ControlAffineRegressor
+        start = ControlAffineRegressor(n, 1, device=dev, dtype=torch.float64)
+    hyper = start._hyper() if hasattr(start, "_hyper") else start
+    hyper = {k: hyper[k].to(**f).expand(Bt, *hyper[k].shape[1:]).clone().contiguous() for k in ("ell", "s2", "Bm", "M0", "A")}
+    # ---- stream rows, subset buffers, the two flat factor buffers
+    Nmax = min(max_train, max(numSteps - 2, 1))
+    Xall, UHall, Yall = (torch.zeros(Bt, numSteps, 2, **f) for _ in range(3))
+    flat = lambda k: torch.empty(Bt * k, **f)
+    sX, sUH, sY, sJ = flat(Nmax * n), flat(Nmax * C), flat(Nmax * n), flat(Nmax)
+    bufs = [dict(Lop=flat(ops.lop_elems(Nmax, torch.float64)), UHB=flat(Nmax * C), Vw=flat(Nmax * n)) for _ in range(2)]
+    info, info2 = (torch.zeros(Bt, dtype=torch.int32, device=dev) for _ in range(2))
+    fail_count = torch.zeros((), dtype=torch.int64, device=dev)
+    retry_counts = torch.zeros(retry_levels + 1, dtype=torch.int64, device=dev)
+    ws = ops.pendulum_workspace(Bt, torch.float64, dev)
+    min_h = torch.full((Bt,), float("inf"), **f)
+    fails = torch.zeros(Bt, dtype=torch.int32, device=dev)
+    bf = None
+    if fit_iters and schedule:
+        from .batched_fit import BatchedHyperFit
+        if hasattr(start, "model"):             # a regressor: its raw parameters (the façade's parametrisation)
+            theta = BatchedHyperFit.from_models([start.model], dtype=torch.float64, device=dev).theta
+            bf = BatchedHyperFit(theta.expand(Bt, -1).contiguous(), n, 1, gamma_length_scale_prior=gamma_length_scale_prior)
+        else:
+            bf = BatchedHyperFit.from_values(hyper["A"], hyper["Bm"], hyper["ell"], hyper["s2"], hyper["M0"], dtype=torch.float64)
+            bf.gamma_length_scale_prior = gamma_length_scale_prior
+    kw = dict(mean_model=mean_model, true_model=true_model, dt=dt, theta_c=cbf_col_theta, delta_c=cbf_col_delta,
+              k_alpha=k_alpha, max_unsafe_prob=max_unsafe_prob, max_iters=max_iters, hessian_mode=hessian_mode,
+              stats=(min_h, fails), ctrl_range=ctrl_range, observe=True)
+    ex = explore[0] if egreedy is not None else None          # (each call passes its step's [Bt,2] slice)
+    step = ops.pendulum_control_step_prepare(dict(hyper), ws, x, prior=True, explore=ex, **kw)
+    model = None
+    rec = None
+    if record:
+        rec = dict(traj=torch.empty(numSteps + 1, Bt, 2, **f), u=torch.empty(numSteps, Bt, **f),
+                   u_ref=torch.empty(numSteps, Bt, **f), status=torch.empty(numSteps, Bt, dtype=torch.int32, device=dev))
+        rec["traj"][0] = x
+    E_ = lambda: torch.cuda.Event(enable_timing=True)
+    ev_refit = [(E_(), E_()) for _ in schedule]
+    refits, final = [], None
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter()
+    k = 0
+    for t in range(numSteps):
+        eps = epsilon(t, interpolate={0: egreedy[0], numSteps: egreedy[1]}) if egreedy is not None else 0.0
+        step(eps=eps, explore=explore[t] if ex is not None else None, obs=(Xall[:, t], UHall[:, t], Yall[:, t], numSteps))
+        if record:
+            rec["traj"][t + 1] = x
+            rec["u"][t] = ws["u"][:, 0]
+            rec["u_ref"][t] = ws["u_ref"][:, 0]
+            rec["status"][t] = ws["status"]
+        if k < len(schedule) and schedule[k][0] == t:
+            _, count, wr = schedule[k]
+            N = min(count, max_train)
+            ev_refit[k][0].record()
+            X, UH, Y, J = sX[:Bt * N * n].view(Bt, N, n), sUH[:Bt * N * C].view(Bt, N, C), sY[:Bt * N * n].view(Bt, N, n), sJ[:Bt * N].view(Bt, N)
+            if wr:
+                idx = refit_draws[k]["idx"].to(dev)[:, :, None].expand(Bt, N, 2)
+                torch.gather(Xall[:, :count], 1, idx, out=X)
+                torch.gather(UHall[:, :count], 1, idx, out=UH)
+                torch.gather(Yall[:, :count], 1, idx, out=Y)
+            else:
+                X.copy_(Xall[:, :N]); UH.copy_(UHall[:, :N]); Y.copy_(Yall[:, :N])
+            torch.mul(refit_draws[k]["jitter"].to(**f), 1e-5, out=J)                  # make_psd: 1e-5 * rand(N)
+            if bf is not None:
+                # the fit's draws (make_psd's jitter, the 1 + 1e-6 rand target perturbation): the loop's generator, replayed
+                # from `draws` or logged into them (record) per iteration
+                rd, log = refit_draws[k], None
+                if "fit_jitter" in rd:
+                    jt, tt = iter(rd["fit_jitter"]), iter(rd["fit_target"])
+                    bf.jitter_rand = lambda idx, N_, jt=jt: next(jt).to(**f)[idx]
+                    bf.target_rand = lambda Y_, tt=tt: next(tt).to(**f)
+                else:
+                    if record:
+                        log = dict(fit_jitter=[], fit_target=[])
+
+                    def draw(key, *shape, log=log):
+                        r = torch.rand(*shape, generator=gen, **f)
+                        if log is not None:
+                            log[key].append(r)
+                        return r
+                    bf.jitter_rand = lambda idx, N_: draw("fit_jitter", Bt, N_)[idx]
+                    bf.target_rand = lambda Y_: draw("fit_target", *Y_.shape)
+                bf.fit(X, UH[:, :, 1:].contiguous(), Y, training_iter=fit_iters, lr=fit_lr)
+                if log is not None:
+                    rd.update(log)
+                hp = bf.derive()
+                for key in ("ell", "s2", "Bm", "M0", "A"):
+                    hyper[key].copy_(hp[key])
+            b_ = bufs[k % 2]
+            E = ops.lop_elems(N, torch.float64)
+            Lop, UHB, Vw = b_["Lop"][:Bt * E].view(Bt, E), b_["UHB"][:Bt * N * C].view(Bt, N, C), b_["Vw"][:Bt * N * n].view(Bt, N, n)
+            ops.refit_with_retries(X, UH, hyper["Bm"], hyper["ell"], hyper["s2"], J, (Lop, UHB, info), levels=retry_levels,
+                                   scratch=info2, counts=retry_counts)
+            ops.potrs(Lop, Y, UH, hyper["M0"], want_alpha=False, out_Vw=Vw)
+            fail_count += (info != 0).sum()
+            model = dict(Lop=Lop, Vw=Vw, X=X, UHB=UHB, **hyper)
+            step = ops.pendulum_control_step_prepare(model, ws, x, explore=ex, **kw)
+            ev_refit[k][1].record()
+            refits.append((t, N))
+            final = dict(X=X, UH=UH, Y=Y, jitter=J)
+            k += 1
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter() - t_loop
+    collided = ~(min_h >= 0)
+    stats = reduce_rollout_stats(collided.sum(), min_h.min(), 0.0, (fails > 0).sum(), Bt)
+    refit_ms = [a_.elapsed_time(b_) for a_, b_ in ev_refit]
+    report = dict(batch=Bt, steps=numSteps, dt=dt, train_every=train_every, max_train=max_train, fit_iters=fit_iters,
+                  learning=bool(learning), mean_model=mean_model, seconds=t_loop, ms_per_step=t_loop / numSteps * 1e3,
+                  instance_steps_per_s=Bt * numSteps / t_loop,
+                  refit_ms_per_refit=(sum(refit_ms) / len(refit_ms)) if refit_ms else None,
+                  solver_optimal_fraction=1.0 - float(fails.sum()) / (Bt * numSteps),
+                  refit_failures_after_retries=int(fail_count),
+                  instances_factored_per_retry_level=[int(v) for v in retry_counts.tolist()], refits=refits)
+    out = dict(stats=stats, report=report, x_final=x, min_h=min_h, fails=fails, ws=ws)
+    if record:
+        out.update(rec)
+        out["draws"] = dict(explore=explore, refits=refit_draws)
+        out["rows"] = dict(X=Xall, UH=UHall, Y=Yall)
+        if final is not None:
+            final = {key: v.clone() for key, v in final.items()}
+        out["final"] = dict(rows=final, hyper={key: v.clone() for key, v in hyper.items()},
+                            gp=None if model is None else {key: v.clone() for key, v in model.items()})
+    return out

@@ -865,6 +865,35 @@ int bcbf_pendulum_control_step_f64(
     double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
     double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
     int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
+
+/* The same step for a loop that LEARNS its dynamics while it runs (ControlPendulumCBFLearned, pendulum.py:909-961, through
+ * ControlCBFLearned / MeanAdjustedModel, controllers.py:320-378, 665-736; run_pendulum_control_online_learning,
+ * pendulum.py:1041-1048).  Every argument of bcbf_pendulum_control_step_f64 with the same meaning, plus:
+ *   prior (0/1): with Lop == NULL and prior = 1 the task kernel writes the GP prior of a regressor that holds no data
+ *     (cbc2.posterior_for, control_affine_model.py:495-506): Mk = M0' (M0[Bt,1+m,n] required), Bk = s2 Bm, G = 0, Mj = 0,
+ *     then adds the mean model as above; prior = 0 is the no-GP mode of the plain entry.  Ignored when Lop != NULL.
+ *   explore[Bt,2] (device; NULL = no exploration), eps, ctrl_range[2] (HOST lo, hi; NULL = no clip): EpsilonGreedyController
+ *     (controllers.py:269-285) around the greedy u_ref -- u_ref = lo + explore[b,1] (hi - lo) where explore[b,0] < eps, then
+ *     u_ref = max(min(u_ref, hi), lo) (misc.py:287-288).  The program is linearised at, and falls back to, that u_ref.
+ *   obs_x, obs_uh, obs_y (all three or none), obs_ld: the plant kernel writes this step's observation row at row b * obs_ld of
+ *     each ([.,2] rows; obs_ld = the row stride, as bcbf_unicycle_control_step_observe): x_t, (1, u_t) with the applied
+ *     u_t, and (x_{t+1} - x_t) / dt - (f + g u_t)(x_t) of the mean model (zero without one).  The states are the stored,
+ *     theta-wrapped ones (the reference's buffer holds them): a step across theta = +-pi gives a target of size ~2 pi / dt.
+ * BCBF_EINVAL, before any HIP call, for every refusal of the plain entry and: prior not 0/1, prior = 1 without M0 (no GP),
+ * eps NaN or outside [0, 1], explore without ctrl_range, explore with u_ref_in, lo > hi (or NaN), a partial obs set,
+ * obs_ld < 1 with obs rows, a mean model with m l == 0. */
+int bcbf_pendulum_control_step_observe_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
 /* The same control step on a model learned with the opt-in Matern-5/2 data kernel (bcbf_refit_matern52 /
  * bcbf_gp_append_matern52 states): identical arguments; the posterior launch evaluates the Matern kernel (one GP per
  * instance: the streaming kernel; shared_gp: the matrix-core query bcbf_posterior_shared_matern52), the fused task rows /
