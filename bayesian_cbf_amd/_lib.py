@@ -56,6 +56,7 @@ _TSIGS = {
                                            P, P, P, P, c_int, P, c_int, P, P, P],
     "bcbf_potrf": [P, P, P, P, c_int, c_int, P],
     "bcbf_subsample_rows": [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P],
+    "bcbf_trigger_interval": [P] * 8 + [c_double] * 4 + [P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_potrs": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_chol_append": [P, P, P, P, P, c_int, c_int, P],
     "bcbf_gp_append": [P] * 17 + [c_int, c_int, c_int, c_int, P],

@@ -256,6 +256,38 @@ def subsample_rows(keys, X, UH, Y, N, lo=0, P=None, out=None):
     return Xo, UHo, Yo, idx
 
 
+def trigger_interval(x, off, ls, sf, Adiag, uBu, xvel, Lh, r, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, out=None):
+    """Self-triggering interval of B instances in one launch (bcbf_trigger_interval; the per-step body of the reference's
+    unicycle_trigger_interval_compute, trigger_interval.py:128-167): x[B,n], test-point offsets off[Nte,n] shared by the batch
+    (Xtest = off + x is formed in the kernel), ls[Bh,n], sf[Bh], Adiag[Bh,n] with Bh = B or 1 (one model for all instances),
+    uBu[B] = uh' B uh, xvel[B], Lh[B]; r = pdist(grid) of the reference, a scalar.  Returns (Lfh[B], tau[B], Lkd[B,n]) on the
+    device; out = the same three buffers to write into (no allocation: the call is capturable in a graph)."""
+    _chk(x, off, ls, sf, Adiag, uBu, xvel, Lh)
+    if x.dim() != 2 or off.dim() != 2 or off.shape[1] != x.shape[1]:
+        raise ValueError("trigger_interval: x %s must be [B, n] and off %s [Nte, n]" % (tuple(x.shape), tuple(off.shape)))
+    B, n = x.shape
+    Nte = off.shape[0]
+    Bh = ls.shape[0] if ls.dim() == 2 else -1
+    if ls.dim() != 2 or ls.shape[1] != n or sf.shape != (Bh,) or Adiag.shape != (Bh, n) or Bh not in (1, B):
+        raise ValueError("trigger_interval: ls %s, sf %s, Adiag %s must be [Bh, n], [Bh], [Bh, n] with Bh = B = %d or 1"
+                         % (tuple(ls.shape), tuple(sf.shape), tuple(Adiag.shape), B))
+    if uBu.shape != (B,) or xvel.shape != (B,) or Lh.shape != (B,):
+        raise ValueError("trigger_interval: uBu %s, xvel %s, Lh %s must be [B]" % (tuple(uBu.shape), tuple(xvel.shape), tuple(Lh.shape)))
+    if out is None:
+        out = (torch.empty(B, dtype=x.dtype, device=x.device), torch.empty(B, dtype=x.dtype, device=x.device),
+               torch.empty(B, n, dtype=x.dtype, device=x.device))
+    Lfh, tau, Lkd = out
+    _chk(x, Lfh, tau, Lkd)
+    if Lfh.shape != (B,) or tau.shape != (B,) or Lkd.shape != (B, n) or Lkd.dtype != x.dtype:
+        raise ValueError("trigger_interval: output buffers of the wrong shape / dtype")
+    rc = getattr(lib, "bcbf_trigger_interval" + _suf(x))(_p(x), _p(off), _p(ls), _p(sf), _p(Adiag), _p(uBu), _p(xvel), _p(Lh), float(r),
+                                                         float(deltaL), float(zeta), float(L_alpha), _p(Lkd), _p(Lfh), _p(tau), B, Bh, Nte,
+                                                         n, _stream(x))
+    if rc != 0:
+        raise _lib.BcbfError("bcbf_trigger_interval failed (rc=%d): %s" % (rc, lib.bcbf_last_error().decode()))
+    return Lfh, tau, Lkd
+
+
 def chol_append(Lop, knew, kappa, N):
     _chk(Lop, knew, kappa)
     Bt = Lop.shape[0]

@@ -179,6 +179,34 @@ class ObstacleCBF:
         self.radius = torch.as_tensor(radius, dtype=torch.float64)
         self.term_weights = tuple(term_weights)
 
+    def _offset(self, state):
+        """(x, y) - center and the radius in the state's dtype / device; per-instance centers [Bt,2] against [Bt,Nte,3] states."""
+        c, rad = self.center.to(state), self.radius.to(state)
+        if c.dim() == 2 and state.dim() == 3:
+            c, rad = c[:, None, :], rad.reshape(-1, 1)
+        return state[..., :2] - c, rad
+
+    def cbf(self, state):
+        """h(x) = w0 (|p - c|^2 - R^2) + w1 cos(alpha - theta), alpha the bearing of p - c (:624-640); state [..., 3]."""
+        g, rad = self._offset(state)
+        gn = g / g.norm(dim=-1, keepdim=True)
+        th = state[..., 2]
+        w0, w1 = self.term_weights
+        return w0 * ((g ** 2).sum(-1) - rad ** 2) + w1 * (th.cos() * gn[..., 0] + th.sin() * gn[..., 1])
+
+    def grad_cbf(self, state):
+        """Gradient of `cbf` (:642-696).  For one state [3] it is the analytic gradient.  On a batch [Nte,3] the reference takes
+        rho = torch.norm(...) over the (x, y) offsets of the WHOLE batch (:670), and the trigger-interval computation reads that
+        (trigger_interval.py:159): kept.  [B,Nte,3]: rho per instance."""
+        g, _ = self._offset(state)
+        rho2 = (g ** 2).sum(dim=(-2, -1), keepdim=True).squeeze(-1) if g.dim() >= 2 else (g ** 2).sum()
+        th = state[..., 2]
+        al = torch.atan2(g[..., 1], g[..., 0])
+        w0, w1 = self.term_weights
+        s = (al - th).sin()
+        return torch.stack([w0 * 2 * g[..., 0] + w1 * s * g[..., 1] / rho2, w0 * 2 * g[..., 1] - w1 * s * g[..., 0] / rho2,
+                            -w1 * (th - al).sin()], dim=-1)
+
 
 def obstacles_at_mid_from_start_and_goal(x, x_g, term_weights=(0.5, 0.5)):
     """unicycle_move_to_pose.py:1562-1570 (x, x_g: [3] or [Bt,3])."""
@@ -478,8 +506,12 @@ def track_trajectory_ackerman_clf_bayesian(x, x_g, dt=None, cbfs=None, cbf_gamma
                                            enable_learning=True, mean_dynamics_gen=lambda: AckermannDrive(L=10.0),
                                            true_dynamics_gen=lambda: AckermannDrive(L=1.0), visualizer_class=None,
                                            controller_class=None, train_every_n_steps=20, logger=None, device="cuda",
-                                           dtype=torch.float64, learned_dynamics=None, training_iter=100, **kw):
-    """:1689-1733.  Returns (X[numSteps+1,3], U[numSteps,2]); `logger` (a tblog.TBLogger) receives every step."""
+                                           dtype=torch.float64, learned_dynamics=None, training_iter=100, log_model=False, **kw):
+    """:1689-1733.  Returns (X[numSteps+1,3], U[numSteps,2]); `logger` (a tblog.TBLogger) receives every step.
+    log_model=True (with a logger and a learned model): every step also logs what the reference's controller attaches for the
+    trigger-interval computation (:970-978) -- `xtp1` = x + fu_func_gp(u).mean(x) dt, the model's one-step prediction, and
+    `knl_lengthscale`, `knl_scalefactor`, `knl_A`, `knl_B` from `get_kernel_param` -- so that
+    `trigger_interval.unicycle_trigger_interval_compute` can read the run.  Off by default: the log is unchanged."""
     from . import tblog
     controller_class = controller_class or ControllerCLFBayesian
     f = dict(dtype=dtype, device=device)
@@ -494,12 +526,21 @@ def track_trajectory_ackerman_clf_bayesian(x, x_g, dt=None, cbfs=None, cbf_gamma
                             clf=CLFCartesian(Kp=[0.9, 1.5, 0.0]), cbfs=cbfs(x, x_g), cbf_gammas=list(cbf_gammas),
                             device=device, dtype=dtype, **kw)
     rl = tblog.RolloutLogger(planner, dt, logger) if logger is not None else None
+    if log_model and rl is not None and dynamics is None:
+        raise ValueError("log_model=True logs the learned model's kernel parameters: it needs enable_learning=True")
     X = torch.empty(numSteps + 1, 3, **f)
     U = torch.empty(numSteps, 2, **f)
     X[0] = x
     for t in range(numSteps):
         u = ctrl.control(X[t], t)
         if rl is not None:
+            if log_model:
+                with torch.no_grad():
+                    xdot = (mean_dynamics.f_func(X[t]) + mean_dynamics.g_func(X[t]) @ u
+                            + dynamics.learned_dynamics.fu_func_gp(u).mean(X[t]))      # the sum GP of :388-394, at the raw state
+                rl.add_info(t, "xtp1", X[t] + xdot * dt)
+                for name in ("lengthscale", "scalefactor", "A", "B"):
+                    rl.add_info(t, "knl_" + name, dynamics.get_kernel_param(name).detach())
             rl.setStateCtrl(X[t], u, t)
         X[t + 1] = X[t] + (plant.f_func(X[t]) + plant.g_func(X[t]) @ u) * dt          # AckermannDrive.step (:277-282)
         U[t] = u

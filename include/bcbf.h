@@ -144,6 +144,28 @@ int bcbf_subsample_rows_f64(const float* keys, int ldk, int lo, int P, const dou
                             int Ntot, int n, int m, int N, double* Xo, double* UHo, double* Yo, int32_t* idx_out, int B,
                             void* stream);
 
+/* Self-triggering interval of B instances in one launch: the high-probability Lipschitz constant Lfh of the learned dynamics
+ * over the test points Xtest = off[Nte,n] + x[b] and the time tau for which the last control stays safe -- the per-step body of
+ * unicycle_trigger_interval_compute (bayes_cbf/trigger_interval.py:128-167; rbf_knl / rbf_d*_knl_d_x_xp_i :32-43), RBF data
+ * kernel only.  Per instance, E = n:
+ *   Lkd[j]     = max over ordered pairs (a, b) of uBu 2 ls_j^-4 (X_a - X_b)_j sf^2 exp(-1/2 sum_d ((X_a - X_b)_d / ls_d)^2)   (:144-147;
+ *                sf is squared as the reference executes it, :33; the pairs a == b count, so Lkd >= 0)
+ *   maxk[i,j]  = Adiag[i] uBu sf^2 / ls_j^2                                                                                (:143)
+ *   Lfs[i,j]   = sqrt(2 log(2 E^2 / deltaL)) maxk + 12 sqrt(6 E) max(maxk, sqrt(r Adiag[i] Lkd[j]))                        (:148-149)
+ *   Lfh        = ||Lfs||_F / E                                                                                             (:151)
+ *   tau        = (1 / Lfh) log(1 + Lfh zeta / ((Lfh + L_alpha) Lh xvel))        (:165; IEEE results such as inf pass through)
+ * x[B,n]; off[Nte,n] shared by the batch, arbitrary points; ls[Bh,n], sf[Bh], Adiag[Bh,n] with Bh = B (per-instance models) or
+ * 1 (one model for all); uBu[B] = uh' B uh, xvel[B], Lh[B]; r = the reference's pdist(grid) scalar.  Outputs Lkd[B,n], Lfh[B],
+ * tau[B].  The pair maximum runs in the working type, the closed forms in fp64 for both.  One workgroup per instance, the
+ * points in LDS: Nte 4 sizeof(T) (n = 3) must fit 160 KB - 256 B.  Limits: B >= 1, Bh in {1, B}, 1 <= n <= 3, Nte >= 1;
+ * otherwise BCBF_EINVAL before any launch, reason in bcbf_last_error.  No allocation, no host synchronisation: capturable. */
+int bcbf_trigger_interval_f32(const float* x, const float* off, const float* ls, const float* sf, const float* Adiag,
+                              const float* uBu, const float* xvel, const float* Lh, double r, double deltaL, double zeta,
+                              double L_alpha, float* Lkd, float* Lfh, float* tau, int B, int Bh, int Nte, int n, void* stream);
+int bcbf_trigger_interval_f64(const double* x, const double* off, const double* ls, const double* sf, const double* Adiag,
+                              const double* uBu, const double* xvel, const double* Lh, double r, double deltaL, double zeta,
+                              double L_alpha, double* Lkd, double* Lfh, double* tau, int B, int Bh, int Nte, int n, void* stream);
+
 /* K2 on a caller-supplied dense SPD matrix (lower triangle of Kb[Bt,N,N] is read): same outputs.
  * Replaces torch.linalg.cholesky (control_affine_model.py:911). */
 int bcbf_potrf_f32(const float* Kb, float* Lop, float* Ldense, int* info, int Bt, int N, void* stream);
