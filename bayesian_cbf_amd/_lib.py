@@ -54,6 +54,9 @@ _TSIGS = {
     "bcbf_predict_fullmat": [P] * 17 + [c_int] * 5 + [P],
     "bcbf_unicycle_control_step_observe": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int,
                                            P, P, P, P, c_int, P, c_int, P, P, P],
+    "bcbf_unicycle_control_step_sampled": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int,
+                                           P, P, P, P, c_int, P, c_int, c_int, P, P, P, P, P, P],
+    "bcbf_rollout_risk": [P, P, P, P, P, c_int, c_int, P],
     "bcbf_potrf": [P, P, P, P, c_int, c_int, P],
     "bcbf_subsample_rows": [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P],
     "bcbf_trigger_interval": [P] * 8 + [c_double] * 4 + [P, P, P, c_int, c_int, c_int, c_int, P],

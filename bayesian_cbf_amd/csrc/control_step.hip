@@ -91,3 +91,53 @@ BCBF_CTRL(double, f64, bcbf_unicycle_control_step_rbfm52_, bcbf_posterior_query_
     }
 BCBF_CTRL_OBS(float, f32)
 BCBF_CTRL_OBS(double, f64)
+
+// The control step with the plant DRAWN FROM THE MODEL'S OWN POSTERIOR (fu_func_gp(u), unicycle_move_to_pose.py:262-275, sampled
+// as GaussianProcessBase.sample samples it, gp_algebra.py:33-34): a solved instance advances by
+//   xdot_s = fhat + ghat u + M_k ubar + sqrt(max(ubar' B_k ubar, 0)) L_A z,   A = L_A L_A',   ubar = (1, u)
+// instead of by the true Ackermann drive (L_true is ignored), and row k's condition is evaluated on the draw,
+// cbc_s[b,k] = sign_k (grad_k . xdot_s + cst_k) (cbc1.py:10-14) -- what the chance constraint bounds the probability of.
+// Arguments of bcbf_unicycle_control_step_observe (the observation rows then record the SAMPLED plant), plus kernel_kind (0 = RBF,
+// 1 = Matern-5/2, 2 = RBF x Matern-5/2: which posterior launch runs) and z[Bt,3] (the caller's standard-normal draws),
+// xdot_s[Bt,3], cbc_s[Bt,1+Kob] (both optional).  Same two launches; the solve launch is the kernel's sampled instantiation.
+#define BCBF_CTRL_SAMPLED(T, SUF)                                                                                      \
+    extern "C" int bcbf_unicycle_control_step_sampled_##SUF(                                                           \
+        const T* Lop, const T* Vw, const T* X, const T* UHB, const T* ell, const T* s2, const T* Bm, const T* M0,     \
+        const T* A, T* x, const T* plan, const T* dot_plan, const T* Kp, T clf_gamma, const T* centers,               \
+        const T* radii, const T* tw, const T* gammas, T L_mean, const T* w, const T* r, const T* sign,                \
+        const T* relax_mask, const T* rho, T* grad, T* cst, T* fhat, T* ghat, T* Mk, T* Bk, T* cones, int* cstatus,   \
+        T* y, int* status, int* iters, T dt, T L_true, int Bt, int N, int Kob, int max_iters, int shared_gp,          \
+        const T* xq, T* obs_x, T* obs_uh, T* obs_y, int obs_ld, T* xq_next, int flags, int kernel_kind,               \
+        const T* z, T* xdot_s, T* cbc_s, void* ev_start, void* ev_stop, void* stream) {                                \
+        if (Bt <= 0) return BCBF_OK;                                                                                   \
+        if (!x || !z || Kob < 0 || Kob + 1 > BCBF_MAX_QUAD_CONSTRAINTS || kernel_kind < 0 || kernel_kind > 2)          \
+            return BCBF_EINVAL;                                                                                        \
+        if ((obs_x || obs_uh || obs_y) && (!obs_x || !obs_uh || !obs_y || obs_ld < 1 || !(dt > T(0)))) return BCBF_EINVAL;   \
+        if (grad && (!cst || !fhat || !ghat)) return BCBF_EINVAL;                                                      \
+        hipStream_t st = (hipStream_t)stream;                                                                          \
+        if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);                                                  \
+        const T* q = xq ? xq : x;                                                                                      \
+        const int sh = shared_gp ? 1 : 0;                                                                              \
+        int rc = BCBF_OK;                                                                                              \
+        if (Lop && kernel_kind == 1)                                                                                   \
+            rc = bcbf_posterior_query_matern52_##SUF(Lop, Vw, X, UHB, ell, s2, Bm, M0, q, nullptr, Mk, Bk, nullptr, sh, Bt, N, 3, 2, stream); \
+        else if (Lop && kernel_kind == 2)                                                                              \
+            rc = bcbf_posterior_query_rbfm52_##SUF(Lop, Vw, X, UHB, ell, s2, Bm, M0, q, nullptr, Mk, Bk, nullptr, sh, Bt, N, 3, 2, stream); \
+        else if (Lop && sh)                                                                                            \
+            rc = bcbf_posterior_query_##SUF(Lop, Vw, X, UHB, ell, s2, Bm, M0, q, nullptr, Mk, Bk, nullptr, 1, Bt, N, 3, 2, stream); \
+        else if (Lop)                                                                                                  \
+            rc = bcbf_posterior_step_##SUF(Lop, Vw, X, UHB, ell, s2, Bm, M0, q, nullptr, Mk, Bk, Bt, N, 3, 2, stream); \
+        if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);                                                    \
+        if (rc) return rc;                                                                                             \
+        bcbf::UnicycleTask<T> task;                                                                                    \
+        task.x = x; task.plan = plan; task.dot_plan = dot_plan; task.Kp = Kp; task.centers = centers;                  \
+        task.radii = radii; task.tw = tw; task.gammas = gammas; task.clf_gamma = clf_gamma; task.L_mean = L_mean;      \
+        task.dt = dt; task.L_true = L_true; task.grad = grad; task.cst = cst; task.fhat = fhat; task.ghat = ghat;      \
+        task.Kob = Kob; task.obs_x = obs_x; task.obs_uh = obs_uh; task.obs_y = obs_y; task.obs_ld = obs_ld;            \
+        task.xq_next = xq_next; task.shift_invariant = flags & 1; task.advance_plan = (flags >> 1) & 1;                \
+        task.z = z; task.xdot_s = xdot_s; task.cbc_s = cbc_s;                                                          \
+        return bcbf::launch_unicycle_socp<T>(Mk, Bk, A, sign, w, r, relax_mask, rho, cones, cstatus, y, status, iters, \
+                                             Bt, max_iters, task, stream);                                             \
+    }
+BCBF_CTRL_SAMPLED(float, f32)
+BCBF_CTRL_SAMPLED(double, f64)

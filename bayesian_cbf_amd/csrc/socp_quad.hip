@@ -215,11 +215,34 @@ __device__ inline void chol3_solve(const double (*H)[NV], double* b) {
     }
 }
 
+// What the posterior-drawn plant step needs of the prologue's registers once the program is solved (SAMPLED only: the other
+// instantiations carry an empty struct and compile to what they compiled to without it).
+template <typename T, bool ON> struct SampledKeep {};
+template <typename T> struct SampledKeep<T, true> {
+    T x[3], row[3], cst, g[3][2], Mk[9], Bk[9], A[9];
+    double sg;
+};
+
+// A copy the optimiser cannot see through: the values the sampled epilogue keeps must not tie the prologue's expressions to the
+// epilogue's (the vectoriser would otherwise pair and contract the prologue's fp32 operations differently than in the other
+// instantiations, and the solve would no longer be bit-identical to theirs).
+template <typename V> __device__ inline V opaque_copy(V v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 // FROM_TERMS: build the cone rows from the GP posterior (cbc_terms fused); else read packed cones.
 // UNI (with FROM_TERMS, n = 3, m = 2): the unicycle step in one launch -- each lane also forms its own task row
 // (CLC / obstacle k-1: unicycle_task.h) from the state instead of reading grad/cst/fhat/ghat, and lane 0 advances the
 // plant with the solution (explicit Euler, unicycle_move_to_pose.py:277-282).
-template <typename T, int M_, bool FROM_TERMS, bool UNI>
+// SAMPLED (with UNI): the plant is a draw from the model's own posterior instead of the true Ackermann drive --
+//   xdot_s = fhat + ghat u + M_k ubar + sqrt(max(ubar' B_k ubar, 0)) L_A z,   A = L_A L_A',   ubar = (1, u),   x += xdot_s dt
+// (fu_func_gp(u), unicycle_move_to_pose.py:262-275, drawn as GaussianProcessBase.sample draws, gp_algebra.py:33-34), and lane k
+// evaluates its own condition on the draw, cbc_s = sign_k (grad_k . xdot_s + cst_k) (cbc1.py:10-14).  fp64 from the stored T
+// values, every output rounded to T once.  A pivot <= 0 of the 3x3 Cholesky zeroes its column: a positive-semidefinite A draws
+// in its range.  z is the caller's; draws of different steps are independent, so the marginal at each visited (x_t, u_t) is
+// exact -- all the per-step chance constraint speaks about -- but a trajectory is not one function drawn from the GP.
+template <typename T, int M_, bool FROM_TERMS, bool UNI, bool SAMPLED = false>
 __global__ void __launch_bounds__(64)
 socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __restrict__ cones_in,
                  const T* __restrict__ relax_mask, const T* __restrict__ rho,
@@ -247,6 +270,7 @@ socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __re
     const int bb = inst_ok ? b : Bt - 1;          // out-of-range quads shadow the last instance (no stores)
     const bool active = k < K;
     const int kk = active ? k : 0;
+    [[maybe_unused]] SampledKeep<T, SAMPLED> keep;
 
     // ---- cone rows  G_k [D][NV], h_k [D]
     R G[D][NV], h[D];
@@ -290,6 +314,19 @@ socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __re
                 T urow[3], ucst = T(0), uG[3][2];          // this lane's task row and the prior input matrix
                 unicycle_row_vals<T>(kk, xs[0], xs[1], xs[2], pl, dp, kp, task.clf_gamma, cx, cy, rad, tw0, tw1, gam, urow, ucst);
                 ackermann_g<T>(xs[2], task.L_mean, uG);
+                if constexpr (SAMPLED) {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        keep.x[d] = opaque_copy(xs[d]); keep.row[d] = opaque_copy(urow[d]);
+                        keep.g[d][0] = opaque_copy(uG[d][0]); keep.g[d][1] = opaque_copy(uG[d][1]);
+                    }
+#pragma unroll
+                    for (int a = 0; a < 9; ++a) {
+                        keep.Mk[a] = opaque_copy(Mkl[a]); keep.Bk[a] = opaque_copy(Bkl[a]); keep.A[a] = opaque_copy(Al[a]);
+                    }
+                    keep.cst = opaque_copy(ucst);
+                    keep.sg = opaque_copy(sg);
+                }
 #pragma unroll
                 for (int d = 0; d < BCBF_MAX_STATE_DIM; ++d) gd[d] = d < 3 ? (double)urow[d < 3 ? d : 0] : 0.0;
                 if (inst_ok && active && task.grad != nullptr) {
@@ -658,7 +695,7 @@ socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __re
         for (int i = 0; i < NV; ++i) y[(size_t)b * NV + i] = (T)x[i];
         status[b] = st_code;
         if (iters) iters[b] = it;
-        if (UNI && task.dt > T(0)) {             // plant step with y = [u0, u1, relax] as stored (rounded to T)
+        if (UNI && !SAMPLED && task.dt > T(0)) { // plant step with y = [u0, u1, relax] as stored (rounded to T)
             T* xs = task.x + (size_t)b * 3;
             const T x0 = xs[0], x1 = xs[1], th = xs[2];
             T n0 = x0, n1 = x1, n2 = th, u0 = T(0), u1 = T(0);
@@ -670,6 +707,65 @@ socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __re
                 xs[0] = n0; xs[1] = n1; xs[2] = n2;
             }
             unicycle_observe<T>(task, b, x0, x1, th, n0, n1, n2, u0, u1);
+        }
+    }
+    if constexpr (SAMPLED) {
+        static_assert(UNI, "the sampled plant is the unicycle step's");
+        if (inst_ok && task.dt > T(0)) {         // every lane of the quad forms the same draw; lane k evaluates its own row on it
+            const bool solved = st_code == BCBF_SOCP_OPTIMAL;
+            double xd[3] = {0.0, 0.0, 0.0}, cb = 0.0;
+            T u0 = T(0), u1 = T(0);
+            if (solved) {
+                u0 = (T)x[0]; u1 = (T)x[1];      // y as stored (rounded to T)
+                const double ub[3] = {1.0, (double)u0, (double)u1};
+                double s_ = 0.0;
+#pragma unroll
+                for (int a = 0; a < 3; ++a)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) s_ += ub[a] * (double)keep.Bk[a * 3 + c] * ub[c];
+                const double rs = __builtin_sqrt(fmax(s_, 0.0));
+                double LA[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    double d = (double)keep.A[j * 3 + j];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) if (q < j) d -= LA[j][q] * LA[j][q];
+                    if (d > 0.0) {               // (else: the column stays zero)
+                        const double ljj = __builtin_sqrt(d);
+                        LA[j][j] = ljj;
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) if (i > j) {
+                            double v = (double)keep.A[i * 3 + j];
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) if (q < j) v -= LA[i][q] * LA[j][q];
+                            LA[i][j] = v / ljj;
+                        }
+                    }
+                }
+                const double z0 = (double)task.z[(size_t)b * 3], z1 = (double)task.z[(size_t)b * 3 + 1],
+                             z2 = (double)task.z[(size_t)b * 3 + 2];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    const double gu = (double)keep.g[d][0] * ub[1] + (double)keep.g[d][1] * ub[2];      // fhat = 0
+                    const double mu = (double)keep.Mk[d * 3] + (double)keep.Mk[d * 3 + 1] * ub[1] + (double)keep.Mk[d * 3 + 2] * ub[2];
+                    xd[d] = gu + mu + rs * (LA[d][0] * z0 + LA[d][1] * z1 + LA[d][2] * z2);
+                }
+                cb = keep.sg * ((double)keep.row[0] * xd[0] + (double)keep.row[1] * xd[1] + (double)keep.row[2] * xd[2] + (double)keep.cst);
+            }
+            if (active && task.cbc_s != nullptr) task.cbc_s[(size_t)b * K + k] = (T)cb;
+            if (k == 0) {
+                T nx[3] = {keep.x[0], keep.x[1], keep.x[2]};
+                if (solved) {                    // an instance whose program was not solved keeps its state, as in the true-plant step
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        nx[d] = (T)((double)keep.x[d] + xd[d] * (double)task.dt);
+                        task.x[(size_t)b * 3 + d] = nx[d];
+                    }
+                }
+                if (task.xdot_s != nullptr)
+                    for (int d = 0; d < 3; ++d) task.xdot_s[(size_t)b * 3 + d] = (T)xd[d];
+                unicycle_observe<T>(task, b, keep.x[0], keep.x[1], keep.x[2], nx[0], nx[1], nx[2], u0, u1);
+            }
         }
     }
 }
@@ -695,6 +791,12 @@ static int launch_quad(const T* w, const T* r, const T* cones_in, const T* relax
     const long lanes = (long)Bt * 4;
     dim3 grid((unsigned)((lanes + threads - 1) / threads)), block(threads);
     hipStream_t st = (hipStream_t)stream;
+    if (FROM_TERMS && task != nullptr && task->z != nullptr) {       // the plant drawn from the posterior: its own instantiation
+        hipLaunchKernelGGL((socp_quad_kernel<T, 2, FROM_TERMS, FROM_TERMS, FROM_TERMS>), grid, block, 0, st, w, r, cones_in,
+                           relax_mask, rho, Mk, Bk, A, grad, cst, sign, fhat, ghat, n, terms_out, cones_out, cstatus, y, status,
+                           iters, Bt, K, max_iters, *task);
+        return check_launch("unicycle_socp_sampled");
+    }
     if (FROM_TERMS && task != nullptr) {
         hipLaunchKernelGGL((socp_quad_kernel<T, 2, FROM_TERMS, FROM_TERMS>), grid, block, 0, st, w, r, cones_in, relax_mask,
                            rho, Mk, Bk, A, grad, cst, sign, fhat, ghat, n, terms_out, cones_out, cstatus, y, status, iters,

@@ -69,9 +69,39 @@ __global__ void rollout_stats_kernel(const T* __restrict__ cst, const T* __restr
     }
 }
 
+// Risk bookkeeping of one closed-loop step on a plant drawn from the posterior (bcbf_unicycle_control_step_sampled's cbc_s), one
+// launch: where the program was solved, solved += 1 and per obstacle row k = 1..Kob  viol += (cbc_s_k < 0)  -- a non-finite value
+// counts as a violation -- and min_cbc = min(min_cbc, cbc_s_k).  An unsolved instance took no step: its counters are untouched.
+template <typename T>
+__global__ void rollout_risk_kernel(const T* __restrict__ cbc_s, const int* __restrict__ status, int* __restrict__ viol,
+                                    int* __restrict__ solved, T* __restrict__ min_cbc, int Bt, int Kob) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt || status[b] != 0) return;
+    solved[b] += 1;
+    for (int k = 0; k < Kob; ++k) {
+        T c = cbc_s[(size_t)b * (1 + Kob) + 1 + k];
+        if (!(c - c == T(0))) c = -INFINITY;                  // NaN or +-inf
+        viol[(size_t)b * Kob + k] += c < T(0) ? 1 : 0;
+        const T m = min_cbc[(size_t)b * Kob + k];
+        min_cbc[(size_t)b * Kob + k] = c < m ? c : m;
+    }
+}
+
 }  // namespace bcbf
 
 extern "C" {
+#define BCBF_ROLLOUT_RISK(T, SUF)                                                                                     \
+    int bcbf_rollout_risk_##SUF(const T* cbc_s, const int* status, int* viol, int* solved, T* min_cbc, int Bt, int Kob, \
+                                void* stream) {                                                                       \
+        if (Bt <= 0) return BCBF_OK;                                                                                  \
+        if (!cbc_s || !status || !solved || Kob < 0 || (Kob > 0 && (!viol || !min_cbc))) return BCBF_EINVAL;          \
+        hipLaunchKernelGGL((bcbf::rollout_risk_kernel<T>), dim3((Bt + 255) / 256), dim3(256), 0, (hipStream_t)stream, \
+                           cbc_s, status, viol, solved, min_cbc, Bt, Kob);                                            \
+        return bcbf::check_launch("rollout_risk");                                                                    \
+    }
+BCBF_ROLLOUT_RISK(float, f32)
+BCBF_ROLLOUT_RISK(double, f64)
+#undef BCBF_ROLLOUT_RISK
 #define BCBF_ROLLOUT_STATS(T, SUF)                                                                                    \
     int bcbf_rollout_stats_##SUF(const T* cst, const T* y, const int* status, const T* w, const T* gammas, T* min_h,  \
                                  T* cost, int* fails, int Bt, int Kob, int nv, void* stream) {                        \

@@ -114,6 +114,15 @@ struct UnicycleTask {
     //               planner.py:54-64: a straight line at constant speed) -- `plan` is then written.
     T *obs_x = nullptr, *obs_uh = nullptr, *obs_y = nullptr, *xq_next = nullptr;
     int obs_ld = 1, shift_invariant = 1, advance_plan = 0;
+    // Plant drawn from the model's own posterior (the sampled instantiation of the fused kernel; z == NULL: not wanted).  With
+    // dt > 0 a solved instance advances by ONE draw of xdot | x, u ~ N(fhat + ghat u + M_k ubar, (ubar' B_k ubar) A), ubar = (1, u)
+    // (fu_func_gp(u), unicycle_move_to_pose.py:262-275, sampled as GaussianProcessBase.sample does, gp_algebra.py:33-34), instead
+    // of by the true Ackermann drive; L_true is ignored.
+    //   z      [Bt,3]  standard-normal draws, the caller's (the library draws no random numbers)
+    //   xdot_s [Bt,3]  (optional) the drawn state derivative; 0 for an instance whose program was not solved
+    //   cbc_s  [Bt,K]  (optional) the sampled conditions sign_k (grad_k . xdot_s + cst_k) (cbc1.py:10-14); 0 where not solved
+    const T* z = nullptr;
+    T *xdot_s = nullptr, *cbc_s = nullptr;
 };
 
 // the observation row of one instance (see UnicycleTask): old state (x0, x1, th), new state (n0, n1, n2), applied u

@@ -39,6 +39,28 @@ def reduce_rollout_stats(collisions, min_h, cost_sum, solver_failures, count):
                 min_h=float(mins[0]))
 
 
+def reduce_risk_stats(instance_steps, violations, min_cbc, max_risk):
+    """Final reduction of the per-shard risk bookkeeping of rollouts on a posterior-drawn plant (`ops.rollout_risk`): SUM for the
+    solved instance-steps and the violations of each obstacle row, MIN for the smallest drawn condition of each row.
+    violations / min_cbc: one entry per obstacle (tensors on the rank's device, or lists).  Returns dict(instance_steps,
+    violations (all rows), rate = violations / (instance_steps * rows): the empirical per-condition risk to hold against max_risk,
+    max_risk, per_obstacle = [dict(violations, rate)], min_cbc = [per row])."""
+    viol = torch.as_tensor(violations).detach().reshape(-1)
+    mins = torch.as_tensor(min_cbc).detach().reshape(-1).to(torch.float64)
+    dev = viol.device
+    if dist.is_available() and dist.is_initialized() and dist.get_backend() != "nccl":
+        dev = "cpu"
+    sums = torch.cat([torch.as_tensor([float(instance_steps)], dtype=torch.float64), viol.to("cpu", torch.float64)]).to(dev)
+    mins = mins.to(dev)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+        dist.all_reduce(mins, op=dist.ReduceOp.MIN)
+    n, per = int(sums[0]), [int(v) for v in sums[1:].tolist()]
+    rows = max(len(per), 1)
+    return dict(instance_steps=n, violations=sum(per), rate=sum(per) / max(n * rows, 1), max_risk=float(max_risk),
+                per_obstacle=[dict(violations=v, rate=v / max(n, 1)) for v in per], min_cbc=[float(v) for v in mins.tolist()])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # One launcher for every multi-GPU harness (bench.py = config 3, examples_mc_rollouts.py = config 4,
 # tools/bench_online.py = config 5): `python <script> --gpus N` starts N ranks itself, or runs as one rank of an external

@@ -18,6 +18,16 @@ import torch
 
 
 class GaussianProcessBase:
+    def sample(self, x, sample_shape=torch.Size([])):
+        """A draw of the process at x (gp_algebra.py:33-34): draw for draw what the reference returns under the same seed,
+        through the same torch class (a scalar process gives samples of shape sample_shape + (1,)).  The batched control step draws the same distribution inside its kernel
+        (`ops.unicycle_control_step_prepare(sampled=...)`)."""
+        from torch.distributions import MultivariateNormal
+        mean = torch.as_tensor(self.mean(x))
+        mean = mean.reshape(-1) if mean.dim() == 0 else mean        # (a scalar expression evaluates to 0-d tensors here)
+        knl = torch.as_tensor(self.knl(x, x)).to(mean).reshape(mean.shape[-1], mean.shape[-1])
+        return MultivariateNormal(mean, knl).sample(sample_shape)
+
     def __add__(self, Y):
         return GaussianProcessAddExpr(self, Y)
 
@@ -65,6 +75,10 @@ class DeterministicGP(GaussianProcessBase):
 
     def covar(self, Z, x, xp):
         return x.new_zeros(max(self._shape), max(Z.shape))
+
+    def sample(self, x, sample_shape=torch.Size([])):
+        """The mean, expanded to the sample shape (gp_algebra.py:99-100): nothing is drawn."""
+        return self.mean(x).expand(*sample_shape, -1)
 
 
 class GaussianProcess(GaussianProcessBase):

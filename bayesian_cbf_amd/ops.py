@@ -1202,7 +1202,7 @@ def _unicycle_control_step_composed(gp, task, ws, x, dt, L_true, L_mean, clf_gam
 
 
 def unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=1.0, L_mean=1.0, clf_gamma=10.0, max_iters=100,
-                                  stream=None, observe=None):
+                                  stream=None, observe=None, sampled=None):
     """Bind every argument of `unicycle_control_step` once and return `step(ev_start=None, ev_stop=None)`.
     A closed loop calls the same entry point with the same buffers thousands of times; converting ~40 tensors to
     pointers per call costs more host time than the two launches take on the device for small batches.  The tensors
@@ -1211,15 +1211,25 @@ def unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=1.0, L_mean=1.
     observe = dict(xq=[Bt,3] | None, xq_next=[Bt,3] | None, shift_invariant=True, advance_plan=False): the loop LEARNS FROM ITSELF
     (bcbf_unicycle_control_step_observe; RBF models): the posterior is queried at `xq`, and the solve / plant launch writes this
     step's observation row where the call says -- `step(ev_start, ev_stop, obs=(obs_x, obs_uh, obs_y, ld))`, three-column
-    tensors whose row b * ld is instance b's (ld = 1: [Bt,3] tensors) -- and the next query into `xq_next`."""
+    tensors whose row b * ld is instance b's (ld = 1: [Bt,3] tensors) -- and the next query into `xq_next`.
+    sampled = dict(z=[Bt,3], xdot_s=[Bt,3] | None, cbc_s=[Bt,1+Kob] | None): the plant is DRAWN FROM THE MODEL'S POSTERIOR
+    (bcbf_unicycle_control_step_sampled; any data kernel): a solved instance advances by xdot_s = fhat + ghat u + M_k ubar +
+    sqrt(ubar' B_k ubar) chol(A) z instead of by the true drive (L_true is ignored), cbc_s = sign_k (grad_k . xdot_s + cst_k) is the
+    condition on the draw.  `z` holds the caller's standard-normal draws: refill it in place before every step (the library draws
+    no random numbers).  Draws of different steps are independent -- exact per-step marginals, not one function drawn along the
+    trajectory.  The buffers are the caller's (`control_workspace` does not hold them); combines with `observe`, whose rows then
+    record the sampled plant."""
     gp, A, N, shared = _control_step_args(gp, task, ws, x)
     Bt = x.shape[0]
     Kob = task["centers"].shape[1]
     kernel = gp.get("kernel", "rbf")                       # data kernel of the learned model: "rbf" (the reference's) | "matern52"
     if kernel not in DATA_KERNELS:
         raise ValueError("gp['kernel'] must be one of %s" % (DATA_KERNELS,))
-    if observe is not None and kernel != "rbf":
+    if observe is not None and kernel != "rbf" and sampled is None:
         raise NotImplementedError("the observing control step is built for the reference's RBF data kernel")
+    if sampled is not None:
+        return _control_step_sampled_closure(gp, task, ws, x, A, N, shared, kernel, dt, L_true, L_mean, clf_gamma, max_iters,
+                                             stream, observe, sampled)
     fn = getattr(lib, ("bcbf_unicycle_control_step_observe" if observe is not None else "bcbf_unicycle_control_step" + _KSUF[kernel]) + _suf(x))
     head = (_p(gp["Lop"]), _p(gp["Vw"]), _p(gp["X"]), _p(gp["UHB"]), _p(gp["ell"]), _p(gp["s2"]), _p(gp["Bm"]),
             _p(gp["M0"]), _p(A), _p(x), _p(task["plan"]), _p(task["dot_plan"]), _p(task["Kp"]), clf_gamma,
@@ -1261,6 +1271,57 @@ def unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=1.0, L_mean=1.
         return y
     step.keep = keep
     return step
+
+
+def _control_step_sampled_closure(gp, task, ws, x, A, N, shared, kernel, dt, L_true, L_mean, clf_gamma, max_iters, stream,
+                                  observe, sampled):
+    """`unicycle_control_step_prepare(sampled=...)`: the same closure form and pointer caching on the sampled entry point."""
+    Bt, Kob = x.shape[0], task["centers"].shape[1]
+    z, xdot_s, cbc_s = sampled["z"], sampled.get("xdot_s"), sampled.get("cbc_s")
+    _chk(x, z, xdot_s, cbc_s)
+    if z is None or tuple(z.shape) != (Bt, 3):
+        raise ValueError("sampled['z'] must be a [Bt,3] tensor of standard-normal draws")
+    if (xdot_s is not None and tuple(xdot_s.shape) != (Bt, 3)) or (cbc_s is not None and tuple(cbc_s.shape) != (Bt, 1 + Kob)):
+        raise ValueError("sampled['xdot_s'] is [Bt,3] and sampled['cbc_s'] is [Bt,1+Kob]")
+    fn = getattr(lib, "bcbf_unicycle_control_step_sampled" + _suf(x))
+    head = (_p(gp["Lop"]), _p(gp["Vw"]), _p(gp["X"]), _p(gp["UHB"]), _p(gp["ell"]), _p(gp["s2"]), _p(gp["Bm"]),
+            _p(gp["M0"]), _p(A), _p(x), _p(task["plan"]), _p(task["dot_plan"]), _p(task["Kp"]), clf_gamma,
+            _p(task["centers"]), _p(task["radii"]), _p(task["tw"]), _p(task["gammas"]), L_mean, _p(task["w"]),
+            _p(task["r"]), _p(task["sign"]), _p(task["relax_mask"]), _p(task["rho"]), _p(ws["grad"]), _p(ws["cst"]),
+            _p(ws["fhat"]), _p(ws["ghat"]), _p(ws["Mk"]), _p(ws["Bk"]), _p(ws["cones"]), _p(ws["cstatus"]), _p(ws["y"]),
+            _p(ws["status"]), _p(ws["iters"]), dt, L_true, Bt, N, Kob, max_iters, 1 if shared else 0)
+    obs_cfg = observe or {}
+    xq, xq_next = obs_cfg.get("xq"), obs_cfg.get("xq_next")
+    _chk(x, xq, xq_next)
+    p_xq, p_next = _p(xq), _p(xq_next)
+    flags = (1 if obs_cfg.get("shift_invariant", True) else 0) | (2 if obs_cfg.get("advance_plan", False) else 0)
+    tail = (DATA_KERNELS.index(kernel), _p(z), _p(xdot_s), _p(cbc_s))
+    keep = (dict(gp), dict(task), dict(ws), x, A, stream, observe, dict(sampled))
+    dev, y = x.device, ws["y"]
+    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+
+    def step(ev_start=None, ev_stop=None, obs=None):
+        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
+        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
+        o = (None, None, None, 1) if obs is None else (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
+        rc = fn(*head, p_xq, *o, p_next, flags, *tail, ev0, ev1,
+                fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            check(rc, "bcbf_unicycle_control_step_sampled")
+        return y
+    step.keep = keep
+    return step
+
+
+def rollout_risk(cbc_s, status, viol, solved, min_cbc):
+    """Risk bookkeeping of one step on a posterior-drawn plant (bcbf_rollout_risk): where status == 0, solved += 1,
+    viol[b,k-1] += (cbc_s[b,k] < 0) (non-finite counts) and min_cbc takes the running minimum, in place; one launch."""
+    _chk(cbc_s, min_cbc)
+    Bt, Kob = cbc_s.shape[0], cbc_s.shape[1] - 1
+    if viol.dtype != torch.int32 or solved.dtype != torch.int32 or status.dtype != torch.int32:
+        raise ValueError("rollout_risk: status, viol and solved are int32 tensors")
+    check(getattr(lib, "bcbf_rollout_risk" + _suf(cbc_s))(_p(cbc_s), _p(status), _p(viol), _p(solved), _p(min_cbc), Bt, Kob,
+                                                         _stream(cbc_s)), "bcbf_rollout_risk")
 
 
 class ConcurrentControlLoop:

@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .cbc2 import cbc1_safety_factor
-from .distributed import reduce_rollout_stats
+from .distributed import reduce_risk_stats, reduce_rollout_stats
 from .planner import PiecewiseLinearPlanner
 
 
@@ -37,12 +37,26 @@ def unicycle_task_tensors(Bt, x0, xg, dtype, device, term_weights=(0.7, 0.3), cb
 def monte_carlo_safety_rollouts(Bt, numSteps=200, dt=0.05, gp=None, kernel_diag_A=(1e-2, 1e-2, 1e-2),
                                 L_mean=1.0, L_true=12.0, start=(-3.0, -1.0, -math.pi / 4), goal=(0.0, 0.0, math.pi / 4),
                                 start_noise=0.05, max_risk=0.01, dtype=torch.float64, device="cuda", seed=0,
-                                record=False, max_iters=30, use_graph=False):
+                                record=False, max_iters=30, use_graph=False, plant="true"):
     """Run Bt closed loops for numSteps steps.  `gp`: dict from BatchedControlAffineGP.as_dict() (learned
     residual, one GP per trajectory) or None (fixed-kernel model M_k = 0, B_k = I, A = diag(kernel_diag_A)).
     Returns dict(stats..., x_final[Bt,3], traj (if record)).  Collectives: one, at the end.
     use_graph: capture one closed-loop step (plan row gather, the fused control step, the safety bookkeeping) in a HIP
-    graph and replay it numSteps times -- the loop is launch bound for small batches (about ten launches per step)."""
+    graph and replay it numSteps times -- the loop is launch bound for small batches (about ten launches per step).
+    plant: "true" (default) -- the deterministic Ackermann drive x += g(x; L_true) u dt -- or "posterior": every step's plant is a
+    draw from the model's OWN posterior, xdot ~ N(fhat + ghat u + M_k ubar, (ubar' B_k ubar) A) (`ops.unicycle_control_step_prepare`
+    with `sampled`; L_true is ignored), which is the distribution the controller's chance constraint P(CBC_k >= 0) >= 1 - max_risk
+    is stated under.  The standard normals z_all[numSteps,Bt,3] are drawn once from the seeded device generator, after the start
+    noise; row t is gathered like the plan row, so the same seed gives the same trajectories eager and under use_graph.  The
+    result gains risk = dict(instance_steps, violations, rate, max_risk, per_obstacle, min_cbc) (`distributed.reduce_risk_stats`):
+    over the solved instance-steps, how often an obstacle row's condition was negative ON THE DRAW -- the empirical risk to hold
+    against max_risk -- and, with record, cbc_s[numSteps,Bt,1+Kob] and status[numSteps,Bt], the drawn conditions and the solver's
+    status of every step.  Draws of different steps
+    are independent: each step's marginal at the visited (x_t, u_t) is exact, which is all the per-step constraint speaks about; a
+    trajectory is NOT one function drawn from the GP (that would mean conditioning on the earlier draws, `ops.gp_append`)."""
+    if plant not in ("true", "posterior"):
+        raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    sampled = plant == "posterior"
     dev = torch.device(device)
     f = dict(dtype=dtype, device=dev)
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -68,8 +82,19 @@ def monte_carlo_safety_rollouts(Bt, numSteps=200, dt=0.05, gp=None, kernel_diag_
     plan_all = torch.stack([planner.plan(t).to(dtype=dtype) for t in range(numSteps)]).to(dev)
     dplan_all = torch.stack([planner.dot_plan(t).to(dtype=dtype) for t in range(numSteps)]).to(dev)
     task["plan"], task["dot_plan"] = torch.empty(Bt, 3, **f), torch.empty(Bt, 3, **f)
+    state = [x, min_h, cost, fails]                        # what a step changes (saved / restored around the graph capture)
+    draw = None
+    if sampled:
+        z_all = torch.randn(numSteps, Bt, 3, generator=gen, **f)
+        draw = dict(z=torch.empty(Bt, 3, **f), xdot_s=torch.zeros(Bt, 3, **f), cbc_s=torch.zeros(Bt, 3, **f))
+        viol = torch.zeros(Bt, 2, dtype=torch.int32, device=dev)
+        solved = torch.zeros(Bt, dtype=torch.int32, device=dev)
+        min_cbc = torch.full((Bt, 2), float("inf"), **f)
+        cbc_traj = torch.empty(numSteps, Bt, 3, **f) if record else None
+        status_traj = torch.empty(numSteps, Bt, dtype=torch.int32, device=dev) if record else None
+        state += [viol, solved, min_cbc]
     step = ops.unicycle_control_step_prepare(gp if gp is not None else fixed, task, ws, x, dt=dt, L_true=L_true,
-                                             L_mean=L_mean, max_iters=max_iters)
+                                             L_mean=L_mean, max_iters=max_iters, sampled=draw)
     import time
     w_cost = task["w"]
 
@@ -78,33 +103,39 @@ def monte_carlo_safety_rollouts(Bt, numSteps=200, dt=0.05, gp=None, kernel_diag_
         if torch.is_tensor(t):
             task["plan"].copy_(plan_all.index_select(0, t))
             task["dot_plan"].copy_(dplan_all.index_select(0, t))
+            if sampled:
+                draw["z"].copy_(z_all.index_select(0, t)[0])
         else:
             task["plan"].copy_(plan_all[t])
             task["dot_plan"].copy_(dplan_all[t])
+            if sampled:
+                draw["z"].copy_(z_all[t])
         step()       # one host call, two launches (one for the fixed-kernel model): rows -> terms -> SOCP -> plant step
         # safety bookkeeping in ONE launch: min_h over the obstacle rows h_k(x_t) = cst_k / gamma_k (before the step; a
         # non-finite h counts as a collision), and -- only where the program was solved: an unsolved program (MAXITER /
         # infeasible / bad cone) is where the reference raises ValueError (unicycle_move_to_pose.py:954-964), the kernel
         # leaves that instance's state untouched for the step and its y is not a control -- the cost; else a failure count
         ops.rollout_stats(ws["cst"], ws["y"], ws["status"], w_cost, gam, min_h, cost, fails)
+        if sampled:      # ... and the risk bookkeeping on the drawn conditions, one more launch
+            ops.rollout_risk(draw["cbc_s"], ws["status"], viol, solved, min_cbc)
 
     torch.cuda.synchronize(dev)
     graph = None
     if use_graph and not record:
         tctr = torch.zeros(1, dtype=torch.long, device=dev)
         side = torch.cuda.Stream(device=dev)
-        saved = [v.clone() for v in (x, min_h, cost, fails)]
+        saved = [v.clone() for v in state]
         with torch.cuda.stream(side):                   # warm-up on the capture stream (allocator, lazy module load)
             one_step(tctr)
         side.synchronize()
-        for dst, src in zip((x, min_h, cost, fails), saved):
+        for dst, src in zip(state, saved):
             dst.copy_(src)
         tctr.zero_()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
             one_step(tctr)
             tctr.add_(1)
-        for dst, src in zip((x, min_h, cost, fails), saved):    # capture does not execute, but keep the state explicit
+        for dst, src in zip(state, saved):    # capture does not execute, but keep the state explicit
             dst.copy_(src)
         tctr.zero_()
         torch.cuda.synchronize(dev)
@@ -116,12 +147,18 @@ def monte_carlo_safety_rollouts(Bt, numSteps=200, dt=0.05, gp=None, kernel_diag_
             one_step(t)
         if record:
             traj[t + 1] = x
+            if sampled:
+                cbc_traj[t] = draw["cbc_s"]
+                status_traj[t] = ws["status"]
     torch.cuda.synchronize(dev)
     t_loop = time.perf_counter() - t_loop
     collided = ~(min_h >= 0)                       # NaN-safe: anything that is not provably >= 0 is a collision
     stats = reduce_rollout_stats(collided.sum(), min_h.min(), cost.sum() / numSteps, (fails > 0).sum(), Bt)
     dist_to_goal = (x[:, :2] - xg[:2]).norm(dim=1)
-    return dict(stats=stats, x_final=x, min_h=min_h, dist_to_goal=dist_to_goal, traj=traj, loop_seconds=t_loop)
+    out = dict(stats=stats, x_final=x, min_h=min_h, dist_to_goal=dist_to_goal, traj=traj, loop_seconds=t_loop)
+    if sampled:
+        out.update(risk=reduce_risk_stats(solved.sum(), viol.sum(0), min_cbc.min(0).values, max_risk), cbc_s=cbc_traj, status=status_traj)
+    return out
 
 
 def online_pass_bytes(N, n, m, itemsize):

@@ -80,6 +80,59 @@ def _fixed_kernel_gp(model, u, name):
     return GaussianProcess(mean=mean, knl=knl, shape=(model.state_size,), name=name, source=(model, "fu", u))
 
 
+def semidefinite_cholesky(K):
+    """Lower-triangular L with L L' = K for a positive-SEMIdefinite K: a pivot <= 0 zeroes its column instead of failing, so the
+    draw L z stays in the range of K.  The same rule as the 3 x 3 factorisation inside the sampled control step (socp_quad.hip)."""
+    n = K.shape[-1]
+    L = torch.zeros_like(K)
+    for j in range(n):
+        d = K[j, j] - (L[j, :j] * L[j, :j]).sum()
+        if not bool(d > 0):
+            continue
+        L[j, j] = torch.sqrt(d)
+        for i in range(j + 1, n):
+            L[i, j] = (K[i, j] - (L[i, :j] * L[j, :j]).sum()) / L[j, j]
+    return L
+
+
+class PosteriorSampledDynamics:
+    """A plant drawn from a Bayesian dynamics model's OWN posterior, for `sampling.sample_generator_trajectory`: every step
+    takes one draw of xdot | x, u from `model.fu_func_gp(u)` -- xdot = gp.mean(x) + L z, L L' = gp.knl(x, x), z ~ N(0, I) from
+    `generator` -- and advances x += xdot dt.  The one-instance counterpart of the batched sampled control step
+    (`ops.unicycle_control_step_prepare(sampled=...)`, `rollouts.monte_carlo_safety_rollouts(plant="posterior")`); it is what the
+    controller's chance constraint P(CBC >= 0) >= 1 - max_risk is stated about.  Draws of different steps are independent: the
+    marginal at each visited (x_t, u_t) is exact, but the trajectory is not one function drawn from the GP (that would mean
+    conditioning the model on the earlier draws).  `f_func` / `g_func` are the model's means."""
+
+    def __init__(self, model, x0=None, generator=None):
+        self.model, self.generator = model, generator
+        self.current_state = None
+        if x0 is not None:
+            self.set_init_state(x0)
+
+    ctrl_size = property(lambda self: self.model.ctrl_size)
+    state_size = property(lambda self: self.model.state_size)
+
+    def set_init_state(self, x0):
+        self.current_state = torch.as_tensor(x0).clone()
+
+    def f_func(self, x):
+        return self.model.f_func(x)
+
+    def g_func(self, x):
+        return self.model.g_func(x)
+
+    def step(self, u, dt):
+        x = self.current_state
+        gp = self.model.fu_func_gp(u)
+        mean = torch.as_tensor(gp.mean(x)).to(x).reshape(-1)
+        L = semidefinite_cholesky(torch.as_tensor(gp.knl(x, x)).to(x))
+        z = torch.randn(x.shape[-1], generator=self.generator, dtype=x.dtype, device=x.device)
+        xdot = mean + L @ z
+        self.current_state = x + xdot * dt
+        return dict(x=self.current_state, xdot=xdot)
+
+
 class PolarDynamics:
     """The unicycle in polar coordinates relative to the goal, x = (rho, alpha, beta), u = (v, omega)
     (unicycle_move_to_pose.py:143-167): f = 0, g = [[-cos a, 0], [-sin a / rho, 1], [-sin a / rho, 0]]."""

@@ -4,6 +4,7 @@ over the GPUs of one node (contiguous shard per rank, no collective inside the l
 
     python examples_mc_rollouts.py --trajectories 4096 --steps 200
     python examples_mc_rollouts.py --gpus 8 --trajectories 32768 --steps 200 --graph        # starts its 8 ranks itself
+    python examples_mc_rollouts.py --plant posterior --max-risk 0.05 --graph     # plants drawn from the model's posterior: `risk`
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         examples_mc_rollouts.py --gpus 8 --trajectories 32768 --steps 200
 
@@ -30,6 +31,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--max-risk", type=float, default=0.01)
     ap.add_argument("--learned", type=int, default=0, help="N_train of a per-trajectory learned GP (0 = fixed kernel)")
+    ap.add_argument("--plant", choices=["true", "posterior"], default="true",
+                    help="posterior: every step's plant is a draw from the model's own posterior; the JSON line gains `risk`, the "
+                         "empirical rate at which an obstacle condition is negative on the draw, to hold against --max-risk")
     ap.add_argument("--graph", action="store_true", help="replay the closed-loop step from a captured HIP graph")
     ap.add_argument("--shared-learned", type=int, default=0,
                     help="N_train of ONE learned GP queried by every trajectory (matrix-core posterior; N <= 512 in fp64)")
@@ -68,7 +72,7 @@ def main():
     ctx.barrier()
     t0 = time.perf_counter()
     out = monte_carlo_safety_rollouts(b - a, numSteps=args.steps, gp=gp, max_risk=args.max_risk, seed=rank, dtype=dtype,
-                                      device=ctx.device, use_graph=args.graph)      # (its statistics: the one reduction)
+                                      device=ctx.device, use_graph=args.graph, plant=args.plant)      # (its statistics: the one reduction)
     torch.cuda.synchronize()
     el_own = time.perf_counter() - t0
     el, per_rank = ctx.reduce_times(el_own)
@@ -105,7 +109,7 @@ def main():
         gp8 = gp if (gp is None or args.shared_learned) else {k: (v[:n8].contiguous() if torch.is_tensor(v) and v.shape[0] == n_loc else v) for k, v in gp.items()}
         torch.cuda.synchronize()
         out8 = monte_carlo_safety_rollouts(n8, numSteps=args.steps, gp=gp8, max_risk=args.max_risk, seed=rank, dtype=dtype,
-                                           device=ctx.device, use_graph=args.graph)
+                                           device=ctx.device, use_graph=args.graph, plant=args.plant)
         torch.cuda.synchronize()
         extra.update(loop_seconds_at_one_eighth=out8["loop_seconds"], trajectories_at_one_eighth=n8,
                      us_per_step_full=out["loop_seconds"] / args.steps * 1e6, us_per_step_at_one_eighth=out8["loop_seconds"] / args.steps * 1e6,
@@ -113,6 +117,8 @@ def main():
                      note="the loop is latency bound (four lanes per trajectory, one wave per CU at 4096 trajectories): an eighth of the "
                           "trajectories takes nearly the same time per step, so 8 GPUs cannot give 8x on a FIXED 32768-trajectory job; "
                           "C4 is reported weak-scaled (trajectories per GPU fixed)")
+    if args.plant == "posterior":
+        extra.update(plant="posterior", risk=out["risk"])
     if rank == 0:
         print(json.dumps(dict(config="c4: Monte-Carlo safety rollouts (unicycle_bayes_cbf_safe_obstacle recipe)", **extra,
                               trajectories=args.trajectories, steps=args.steps, n_gpus=world, seconds=el, loop_seconds=loop_max,

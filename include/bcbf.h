@@ -288,6 +288,15 @@ int bcbf_rollout_stats_f32(const float* cst, const float* y, const int* status, 
                            float* min_h, float* cost, int* fails, int Bt, int Kob, int nv, void* stream);
 int bcbf_rollout_stats_f64(const double* cst, const double* y, const int* status, const double* w, const double* gammas,
                            double* min_h, double* cost, int* fails, int Bt, int Kob, int nv, void* stream);
+/* Risk bookkeeping of one closed-loop step on a posterior-drawn plant (bcbf_unicycle_control_step_sampled's cbc_s[Bt,1+Kob]),
+ * the empirical side of the chance constraint P(CBC_k >= 0) >= 1 - max_risk (cbc1.py:10-14): where status[b] == 0,
+ * solved[b] += 1, viol[b,k-1] += (cbc_s[b,k] < 0) for the obstacle rows k = 1..Kob (a non-finite value counts as a violation) and
+ * min_cbc[b,k-1] = min(min_cbc[b,k-1], cbc_s[b,k]); an unsolved instance took no step and is left alone.  viol[Bt,Kob] and
+ * solved[Bt] are int32.  One launch, no host look: capturable in a graph. */
+int bcbf_rollout_risk_f32(const float* cbc_s, const int* status, int* viol, int* solved, float* min_cbc, int Bt, int Kob,
+                          void* stream);
+int bcbf_rollout_risk_f64(const double* cbc_s, const int* status, int* viol, int* solved, double* min_cbc, int Bt, int Kob,
+                          void* stream);
 
 /* Capacity-reserving GP storage for the online path (BASELINE configs[4]; the reference refits from scratch,
  * unicycle_move_to_pose.py:340-386).  The packed layout depends on the padded size and X / UH*B / Vw are [Bt,N,.] arrays,
@@ -828,6 +837,42 @@ int bcbf_unicycle_control_step_observe_f64(
     double* Bk, double* cones, int* cstatus, double* y, int* status, int* iters, double dt, double L_true, int Bt,
     int N, int Kob, int max_iters, int shared_gp, const double* xq, double* obs_x, double* obs_uh, double* obs_y,
     int obs_ld, double* xq_next, int flags, void* ev_start, void* ev_stop, void* stream);
+/* The control step on a plant DRAWN FROM THE MODEL'S OWN POSTERIOR.  The program of the step asks that every condition hold
+ * with probability >= 1 - max_risk under xdot | x, u ~ N(fhat + ghat u + M_k ubar, (ubar' B_k ubar) A), ubar = (1, u): the
+ * matrix-variate posterior of fu_func_gp(u) (unicycle_move_to_pose.py:262-275).  This entry draws from that distribution, as
+ * GaussianProcessBase.sample(x) does for one state (gp_algebra.py:33-34), inside the solve / plant launch: for an instance whose
+ * program was solved (status == BCBF_SOCP_OPTIMAL)
+ *     xdot_s = fhat + ghat u + M_k ubar + sqrt(max(ubar' B_k ubar, 0)) L_A z,     x += xdot_s dt       (dt > 0)
+ *     cbc_s[b,k] = sign[k] (grad[b,k,:] . xdot_s + cst[b,k])    k = 0 the CLC row, k >= 1 the obstacles (cbc1.py:10-14)
+ * with u = y as stored, fhat = 0 and ghat = g(x; L_mean) (the rows of bcbf_unicycle_control_step), A = L_A L_A' factored in the
+ * kernel (a pivot <= 0 zeroes its column: a positive-semidefinite A is accepted and draws in its range); fp64 arithmetic on the
+ * stored values, each output rounded once.  An unsolved instance keeps its state; its xdot_s and cbc_s rows are 0.  L_true is
+ * ignored: the plant is the model's belief.  Draws of different steps are independent: the marginal at every visited (x_t, u_t)
+ * is exact, which is all the per-step chance constraint speaks about; a function-consistent draw along a trajectory would have to
+ * condition on the earlier draws (bcbf_gp_append) and is not what this entry does.
+ * Arguments of bcbf_unicycle_control_step_observe -- the observation rows then record the sampled plant -- plus
+ *   kernel_kind   the data kernel of the learned model: 0 = RBF, 1 = Matern-5/2, 2 = RBF x Matern-5/2 (the posterior launch);
+ *   z[Bt,3]       standard-normal draws, the caller's: the library draws no random numbers (as bcbf_subsample_rows);
+ *   xdot_s[Bt,3], cbc_s[Bt,1+Kob]   outputs, each may be NULL. */
+int bcbf_unicycle_control_step_sampled_f32(
+    const float* Lop, const float* Vw, const float* X, const float* UHB, const float* ell, const float* s2,
+    const float* Bm, const float* M0, const float* A, float* x, const float* plan, const float* dot_plan,
+    const float* Kp, float clf_gamma, const float* centers, const float* radii, const float* tw, const float* gammas,
+    float L_mean, const float* w, const float* r, const float* sign, const float* relax_mask, const float* rho,
+    float* grad, float* cst, float* fhat, float* ghat, float* Mk, float* Bk, float* cones, int* cstatus,
+    float* y, int* status, int* iters, float dt, float L_true, int Bt, int N, int Kob, int max_iters, int shared_gp,
+    const float* xq, float* obs_x, float* obs_uh, float* obs_y, int obs_ld, float* xq_next, int flags, int kernel_kind,
+    const float* z, float* xdot_s, float* cbc_s, void* ev_start, void* ev_stop, void* stream);
+int bcbf_unicycle_control_step_sampled_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, double* x, const double* plan, const double* dot_plan,
+    const double* Kp, double clf_gamma, const double* centers, const double* radii, const double* tw,
+    const double* gammas, double L_mean, const double* w, const double* r, const double* sign,
+    const double* relax_mask, const double* rho, double* grad, double* cst, double* fhat, double* ghat, double* Mk,
+    double* Bk, double* cones, int* cstatus, double* y, int* status, int* iters, double dt, double L_true, int Bt,
+    int N, int Kob, int max_iters, int shared_gp, const double* xq, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, double* xq_next, int flags, int kernel_kind, const double* z, double* xdot_s, double* cbc_s,
+    void* ev_start, void* ev_stop, void* stream);
 
 /* ---- The pendulum's rel-degree-2 safety loop (SOCPController with cbfs = [RadialCBFRelDegree2], clf = None and the
  * greedy nominal controller: controllers.py:569-591, pendulum.py:643-746), batched: n = 2, m = 1.
