@@ -1,0 +1,207 @@
+// One event of the self-triggered closed loop for every instance in one launch (bcbf_unicycle_trigger_step): the trigger time
+// tau of the control that bcbf_unicycle_control_step (called with dt = 0: solve only) has just left in its workspace, and the
+// plant step over that time.  The periodic loops re-solve every dt; this one re-solves when the model says the last control
+// stops being safe, each instance on its own clock.
+//
+// One workgroup per instance, as in trigger.hip, whose pair loop and closed forms it shares (trigger_pairs.h).  What
+// trigger_interval_batch forms in torch before that launch -- a dozen launches and a [Bt, Nte, 3] tensor per step -- is done
+// here on the test points that are in LDS anyway:
+//   uBu  = ubar' Bhyp ubar, ubar = (1, u), u = y[b, 0:2]                                     one thread, fp64
+//   xvel = |fhat + ghat u + M_k ubar|      the model's one-step prediction over dt            one thread, fp64, M_k ubar formed as the
+//                                                                                             sampled branch of socp_quad_kernel does
+//   Lh   = the largest single element of ObstacleCBF.grad_cbf over test points, obstacles and components, with the reference's
+//          rho^2 = SUM over all test points of |p_a - c_k|^2 (unicycle_move_to_pose.py:670): per obstacle one block sum, then one
+//          block maximum over all of them; wave shuffles, the four waves through LDS, no float atomics.  fp64 in both precisions
+//          (Nte Kob / 256 evaluations per thread against Nte^2 / 512 pairs).
+// Each of the three is rounded to the working type before the closed forms read it, so the results are those of
+// bcbf_trigger_interval fed the same three numbers.  Thread 0 then acts: clamp, Euler step of the true plant (the arithmetic of
+// bcbf_unicycle_step), the instance's clock, its event count and the planner rows of its new time.  An instance whose clock has
+// reached t_end leaves before anything is read or written.
+#include "trigger_pairs.h"
+#include <stdio.h>
+
+namespace bcbf {
+
+template <typename T>
+struct TriggerStepArgs {
+    T* x; const T* y; const int* status; const T* fhat; const T* ghat; const T* Mk;
+    const T* centers; const T* tw; const T* off;
+    const T* ls; const T* sf; const T* Adiag; const T* Bhyp;
+    double r, deltaL, zeta, L_alpha, tau_min, tau_max, t_end;
+    T L_true;
+    const T* plan_all; const T* dplan_all; double dt_plan;
+    double* t; int* events; T* plan; T* dot_plan;
+    T* tau; T* dt_used; T* Lfh; T* Lkd; T* Lh; T* xvel; T* uBu;
+    int per_instance_hyper, Kob, Nte, P;
+};
+
+// sum or maximum of v over the workgroup, through red[slot] (every slot is used once per launch: no barrier after the read)
+__device__ inline double block_reduce(double v, double (*red)[TI_WAVES], int slot, bool is_max) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double w = __shfl_xor(v, o, 64);
+        v = is_max ? fmax(v, w) : v + w;
+    }
+    if ((threadIdx.x & 63) == 0) red[slot][threadIdx.x >> 6] = v;
+    __syncthreads();
+    double out = red[slot][0];
+    for (int w = 1; w < TI_WAVES; ++w) out = is_max ? fmax(out, red[slot][w]) : out + red[slot][w];
+    return out;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const TriggerStepArgs<T> a) {
+    constexpr int NS = 3, ST = ti_stride(NS);
+    extern __shared__ __attribute__((aligned(16))) unsigned char ts_raw[];
+    __shared__ T ts_red[TI_WAVES][NS];
+    __shared__ double ts_sum[BCBF_MAX_CONSTRAINTS][TI_WAVES];      // slot k: rho^2 of obstacle k; the last slot: the maximum
+    T* pts = reinterpret_cast<T*>(ts_raw);
+    const int b = blockIdx.x, hb = a.per_instance_hyper ? b : 0, N = a.Nte;
+    const double t0 = a.t[b];
+    if (t0 >= a.t_end) return;                          // finished (the whole workgroup: nothing of the instance is touched)
+    T xb[NS], q[NS];
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        xb[j] = a.x[(size_t)b * NS + j];
+        q[j] = T(ti_qscale<T>()) / a.ls[(size_t)hb * NS + j];
+    }
+    for (int i = threadIdx.x; i < N; i += TI_THREADS) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) pts[i * ST + j] = a.off[(size_t)i * NS + j] + xb[j];
+    }
+    __syncthreads();
+
+    // Lh: grad_cbf on the [Nte, 3] test points of this instance, per obstacle with its batch-wide rho^2
+    const double w0 = (double)a.tw[0], w1 = (double)a.tw[1];
+    double lh = -INFINITY;
+    for (int k = 0; k < a.Kob; ++k) {
+        const double cx = (double)a.centers[((size_t)b * a.Kob + k) * 2], cy = (double)a.centers[((size_t)b * a.Kob + k) * 2 + 1];
+        double part = 0.0;
+        for (int i = threadIdx.x; i < N; i += TI_THREADS) {
+            const double gx = (double)pts[i * ST] - cx, gy = (double)pts[i * ST + 1] - cy;
+            part += gx * gx + gy * gy;
+        }
+        const double rho2 = block_reduce(part, ts_sum, k, false);
+        for (int i = threadIdx.x; i < N; i += TI_THREADS) {
+            const double gx = (double)pts[i * ST] - cx, gy = (double)pts[i * ST + 1] - cy, th = (double)pts[i * ST + 2];
+            const double al = atan2(gy, gx), s = sin(al - th);
+            lh = fmax(lh, fmax(fmax(w0 * 2.0 * gx + w1 * s * gy / rho2, w0 * 2.0 * gy - w1 * s * gx / rho2), -w1 * sin(th - al)));
+        }
+    }
+    lh = block_reduce(lh, ts_sum, BCBF_MAX_CONSTRAINTS - 1, true);
+
+    ti_pair_max<T, NS>(pts, N, q, ts_red);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+
+    // ubar' Bhyp ubar and the model's predicted velocity, then the closed forms on the three numbers as the working type holds them
+    const T u0 = a.y[(size_t)b * 3], u1 = a.y[(size_t)b * 3 + 1];
+    const double ub[3] = {1.0, (double)u0, (double)u1};
+    double uB = 0.0, v2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) uB += ub[i] * (double)a.Bhyp[(size_t)hb * 9 + i * 3 + c] * ub[c];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const T* g = a.ghat + ((size_t)b * 3 + d) * 2;
+        const T* M = a.Mk + ((size_t)b * 3 + d) * 3;
+        const double gu = (double)g[0] * ub[1] + (double)g[1] * ub[2];
+        const double mu = (double)M[0] + (double)M[1] * ub[1] + (double)M[2] * ub[2];
+        const double v = (double)a.fhat[(size_t)b * 3 + d] + gu + mu;
+        v2 += v * v;
+    }
+    const T uBT = (T)uB, xvT = (T)sqrt(v2), lhT = (T)lh;
+    double lkd[NS], tv;
+    const double L = ti_closed_forms<T, NS>(ts_red, a.ls + (size_t)hb * NS, (double)a.sf[hb], a.Adiag + (size_t)hb * NS, (double)uBT,
+                                            (double)lhT, (double)xvT, a.r, a.deltaL, a.zeta, a.L_alpha, lkd, tv);
+    const T tauT = (T)tv;
+    if (a.uBu) a.uBu[b] = uBT;
+    if (a.xvel) a.xvel[b] = xvT;
+    if (a.Lh) a.Lh[b] = lhT;
+    if (a.Lfh) a.Lfh[b] = (T)L;
+    if (a.tau) a.tau[b] = tauT;
+    if (a.Lkd) {
+        for (int j = 0; j < NS; ++j) a.Lkd[(size_t)b * NS + j] = (T)lkd[j];
+    }
+
+    // act on it: the time this control is held (tau as the working type holds it; +inf -> tau_max, NaN or <= 0 -> tau_min) ...
+    const bool solved = a.status[b] == BCBF_SOCP_OPTIMAL;
+    const double tq = (double)tauT, left = a.t_end - t0;
+    double hold = a.tau_max;                          // an unsolved instance takes no step: time passes as in the periodic loop
+    if (solved) hold = !(tq > 0.0) ? a.tau_min : fmin(fmax(tq, a.tau_min), a.tau_max);
+    const bool last = !(hold < left);
+    const T dtT = (T)(last ? left : hold);
+    if (solved) {                                     // ... the plant over it
+        const T th = xb[2];
+        a.x[(size_t)b * 3] = xb[0] + cos(th) * u0 * dtT;
+        a.x[(size_t)b * 3 + 1] = xb[1] + sin(th) * u0 * dtT;
+        a.x[(size_t)b * 3 + 2] = th + u1 / a.L_true * dtT;
+    }
+    if (a.dt_used) a.dt_used[b] = dtT;
+    // ... the clock (the step taken, as the plant saw it; the last one lands on t_end itself), the count and the planner's rows
+    const double t1 = last ? a.t_end : t0 + (double)dtT;
+    a.t[b] = t1;
+    a.events[b] += 1;
+    const double fi = floor(t1 / a.dt_plan);
+    const int row = fi >= (double)(a.P - 1) ? a.P - 1 : (fi > 0.0 ? (int)fi : 0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        a.plan[(size_t)b * 3 + j] = a.plan_all[(size_t)row * 3 + j];
+        a.dot_plan[(size_t)b * 3 + j] = a.dplan_all[(size_t)row * 3 + j];
+    }
+}
+
+template <typename T>
+static int trigger_step_args_ok(const char* entry, const TriggerStepArgs<T>& a, int Bt, int Bh) {
+    static thread_local char msg[280];
+    const char* why = nullptr;
+    if (!a.x || !a.y || !a.status || !a.fhat || !a.ghat || !a.Mk) why = "null control-step buffer (x, y, status, fhat, ghat, Mk)";
+    else if (!a.centers || !a.tw || !a.off) why = "null input pointer (centers, tw, off)";
+    else if (!a.ls || !a.sf || !a.Adiag || !a.Bhyp) why = "null hyper-parameter pointer (ls, sf, Adiag, Bhyp)";
+    else if (!a.plan_all || !a.dplan_all) why = "null planner table";
+    else if (!a.t || !a.events || !a.plan || !a.dot_plan) why = "null in/out pointer (t, events, plan, dot_plan)";
+    else if (Bt < 1) why = "Bt < 1";
+    else if (Bh != 1 && Bh != Bt) why = "the hyper-parameters' leading extent Bh must be 1 or Bt";
+    else if (a.Kob < 1 || a.Kob > BCBF_MAX_CONSTRAINTS - 1) why = "need 1 <= Kob <= BCBF_MAX_CONSTRAINTS - 1";
+    else if (a.Nte < 1) why = "Nte < 1";
+    else if ((size_t)a.Nte * ti_stride(3) * sizeof(T) > TI_MAX_LDS) why = "Nte too large (the test points of one instance are kept in LDS)";
+    else if (a.P < 1) why = "P < 1";
+    else if (!(a.dt_plan > 0.0)) why = "dt_plan must be positive";
+    else if (!(a.tau_min > 0.0)) why = "tau_min must be positive";
+    else if (!(a.tau_min <= a.tau_max)) why = "tau_min > tau_max";
+    else if (!(a.tau_max < INFINITY)) why = "tau_max must be finite";
+    if (!why) return 1;
+    snprintf(msg, sizeof(msg), "%s: %s (Bt=%d Bh=%d Kob=%d Nte=%d P=%d tau_min=%g tau_max=%g)", entry, why, Bt, Bh, a.Kob, a.Nte, a.P,
+             a.tau_min, a.tau_max);
+    set_error_message(msg);
+    return 0;
+}
+
+template <typename T>
+static int launch_trigger_step(const char* entry, TriggerStepArgs<T> a, int Bt, int Bh, void* stream) {
+    if (!trigger_step_args_ok<T>(entry, a, Bt, Bh)) return BCBF_EINVAL;
+    a.per_instance_hyper = Bh == Bt && Bt > 1 ? 1 : 0;
+    const size_t lds = (size_t)a.Nte * ti_stride(3) * sizeof(T);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((unicycle_trigger_step_kernel<T>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a);
+    return check_launch(entry);
+}
+
+}  // namespace bcbf
+
+#define BCBF_TRIGGER_STEP(T, SUF)                                                                                                 \
+    extern "C" int bcbf_unicycle_trigger_step_##SUF(                                                                              \
+        T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off, \
+        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, \
+        double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, int* events, T* plan, \
+        T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu, int Bt, int Bh, int Kob, int Nte, int P, void* stream) { \
+        bcbf::TriggerStepArgs<T> a = {x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, \
+                                      tau_min, tau_max, t_end, L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, \
+                                      dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P};                                          \
+        return bcbf::launch_trigger_step<T>("bcbf_unicycle_trigger_step_" #SUF, a, Bt, Bh, stream);                               \
+    }
+BCBF_TRIGGER_STEP(float, f32)
+BCBF_TRIGGER_STEP(double, f64)
+#undef BCBF_TRIGGER_STEP

@@ -1405,6 +1405,69 @@ def control_workspace(Bt, Kob, dtype, device, n=3, m=2):
                 y=torch.empty(Bt, m + 1, **f), status=torch.empty(Bt, **i), iters=torch.empty(Bt, **i))
 
 
+def trigger_workspace(Bt, dtype, device):
+    """Buffers of `unicycle_trigger_step_prepare`: every instance's clock t[Bt] (fp64 whatever the working type) and event count
+    events[Bt] (int32), both zero, and the outputs of one event -- tau, dt_used, Lfh, Lkd[Bt,3], Lh, xvel, uBu (zero: a finished
+    instance's rows are never written)."""
+    f = dict(dtype=dtype, device=device)
+    ws = {k: torch.zeros(Bt, **f) for k in ("tau", "dt_used", "Lfh", "Lh", "xvel", "uBu")}
+    ws.update(Lkd=torch.zeros(Bt, 3, **f), t=torch.zeros(Bt, dtype=torch.float64, device=device),
+              events=torch.zeros(Bt, dtype=torch.int32, device=device))
+    return ws
+
+
+def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, dt_plan, t_end, tau_min, tau_max,
+                                  L_true=1.0, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, stream=None):
+    """Bind the buffers of one EVENT of the self-triggered loop once and return `step()` (bcbf_unicycle_trigger_step, one launch):
+    run it after the `step()` of `unicycle_control_step_prepare(..., dt=0)` on the same task / ws / x.  It computes the trigger
+    time tau of the control in ws['y'] (uBu, xvel, Lh, Lkd, Lfh, tau as `trigger_interval.trigger_interval_batch` does, on the test
+    points off[Nte,3] + x), holds the control for dt_b = min(clamp(tau, tau_min, tau_max), t_end - t) on the true plant (unsolved
+    instances keep their state and let min(tau_max, t_end - t) pass), advances tws['t'], tws['events'] and copies the planner rows
+    of the new time, min(floor(t / dt_plan), P - 1) of plan_all[P,3] / dplan_all[P,3], into task['plan'], task['dot_plan'].
+    Instances with t >= t_end are left alone.  hyper = dict(ls[Bh,3], sf[Bh], Adiag[Bh,3], B[Bh,3,3]), Bh = Bt or 1; r = pdist(off)
+    (`trigger_interval._grid_norm`); tws from `trigger_workspace`.  The tensors must keep their storage; the closure keeps them."""
+    Bt = x.shape[0]
+    ls, sf, Adiag, Bh_ = hyper["ls"], hyper["sf"], hyper["Adiag"], hyper["B"]
+    _chk(x, off, ls, sf, Adiag, Bh_, plan_all, dplan_all, task["plan"], task["dot_plan"], task["centers"], task["tw"], ws["y"],
+         ws["fhat"], ws["ghat"], ws["Mk"], tws["tau"], tws["dt_used"], tws["Lfh"], tws["Lkd"], tws["Lh"], tws["xvel"], tws["uBu"])
+    if x.dim() != 2 or x.shape[1] != 3 or off.dim() != 2 or off.shape[1] != 3:
+        raise ValueError("trigger step: x %s must be [Bt, 3] and off %s [Nte, 3]" % (tuple(x.shape), tuple(off.shape)))
+    Bh = ls.shape[0] if ls.dim() == 2 else -1
+    if (tuple(ls.shape), tuple(sf.shape), tuple(Adiag.shape), tuple(Bh_.shape)) != ((Bh, 3), (Bh,), (Bh, 3), (Bh, 3, 3)):
+        raise ValueError("trigger step: ls %s, sf %s, Adiag %s, B %s must be [Bh, 3], [Bh], [Bh, 3], [Bh, 3, 3]"
+                         % (tuple(ls.shape), tuple(sf.shape), tuple(Adiag.shape), tuple(Bh_.shape)))
+    P = plan_all.shape[0]
+    if tuple(plan_all.shape) != (P, 3) or tuple(dplan_all.shape) != (P, 3):
+        raise ValueError("trigger step: plan_all %s and dplan_all %s must be [P, 3]" % (tuple(plan_all.shape), tuple(dplan_all.shape)))
+    Kob = task["centers"].shape[1]
+    if tuple(task["centers"].shape) != (Bt, Kob, 2) or task["tw"].numel() != 2:
+        raise ValueError("trigger step: centers must be [Bt, Kob, 2] and tw [2]")
+    t, events = tws["t"], tws["events"]
+    if t.dtype != torch.float64 or events.dtype != torch.int32 or ws["status"].dtype != torch.int32 or not (
+            t.is_contiguous() and events.is_contiguous() and t.shape == events.shape == (Bt,)):
+        raise ValueError("trigger step: t is a float64 and events an int32 [Bt] tensor")
+    for k in ("tau", "dt_used", "Lfh", "Lh", "xvel", "uBu", "Lkd"):
+        if tuple(tws[k].shape) != ((Bt, 3) if k == "Lkd" else (Bt,)):
+            raise ValueError("trigger step: output buffer %s of the wrong shape" % k)
+    fn = getattr(lib, "bcbf_unicycle_trigger_step" + _suf(x))
+    args = (_p(x), _p(ws["y"]), _p(ws["status"]), _p(ws["fhat"]), _p(ws["ghat"]), _p(ws["Mk"]), _p(task["centers"]), _p(task["tw"]),
+            _p(off), float(r), _p(ls), _p(sf), _p(Adiag), _p(Bh_), float(deltaL), float(zeta), float(L_alpha), float(tau_min),
+            float(tau_max), float(t_end), float(L_true), _p(plan_all), _p(dplan_all), float(dt_plan), _p(t), _p(events),
+            _p(task["plan"]), _p(task["dot_plan"]), _p(tws["tau"]), _p(tws["dt_used"]), _p(tws["Lfh"]), _p(tws["Lkd"]), _p(tws["Lh"]),
+            _p(tws["xvel"]), _p(tws["uBu"]), Bt, Bh, Kob, off.shape[0], P)
+    keep = (dict(task), dict(ws), dict(tws), x, off, dict(hyper), plan_all, dplan_all, stream)
+    dev = x.device
+    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+
+    def step():
+        rc = fn(*args, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            raise _lib.BcbfError("bcbf_unicycle_trigger_step failed (rc=%d): %s" % (rc, lib.bcbf_last_error().decode()))
+        return tws["dt_used"]
+    step.keep = keep
+    return step
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The pendulum's rel-degree-2 safety loop (bcbf_pendulum_control_step_f64): SOCPController(cbfs=[RadialCBFRelDegree2],
 # clf=None) with the greedy nominal controller, one host call per step for a batch of pendulums (fp64).

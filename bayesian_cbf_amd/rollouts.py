@@ -161,6 +161,158 @@ def monte_carlo_safety_rollouts(Bt, numSteps=200, dt=0.05, gp=None, kernel_diag_
     return out
 
 
+def _trigger_hyper(ls, sf, A, B, Bt, f):
+    """ls, sf, A, B of one model or of Bt models -> dict(ls[Bh,3], sf[Bh], Adiag[Bh,3], B[Bh,3,3]) for the trigger step, Bh = 1 or Bt
+    (mixed leading extents are expanded to Bt)."""
+    ls, sf, A, B = (torch.as_tensor(v, **f) for v in (ls, sf, A, B))       # (python numbers go straight to the working type)
+    ls, sf, A, B = ls.reshape(-1, 3), sf.reshape(-1), A.reshape(-1, 3, 3), B.reshape(-1, 3, 3)
+    ext = {v.shape[0] for v in (ls, sf, A, B)}
+    if not ext <= {1, Bt}:
+        raise ValueError("trigger hyper-parameters: ls %s, sf %s, A %s, B %s: one model or one per instance (Bt = %d)"
+                         % (tuple(ls.shape), tuple(sf.shape), tuple(A.shape), tuple(B.shape), Bt))
+    Bh = max(ext)
+    ex = lambda v: v.expand(Bh, *v.shape[1:]).contiguous()
+    return dict(ls=ex(ls), sf=ex(sf), Adiag=ex(torch.diagonal(A, dim1=-2, dim2=-1)), B=ex(B))
+
+
+def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=None, tau_min=1e-3, tau_max=0.05, max_events=None,
+                            kernel_diag_A=(1e-2, 1e-2, 1e-2), L_mean=1.0, L_true=12.0, start=(-3.0, -1.0, -math.pi / 4),
+                            goal=(0.0, 0.0, math.pi / 4), start_noise=0.05, max_risk=0.01, dtype=torch.float64, device="cuda",
+                            seed=0, record=False, max_iters=30, use_graph=False, Nte=1e3, off=None, deltaL=1e-4, zeta=1e-2,
+                            L_alpha=1.0):
+    """The closed loop that ACTS on the self-triggering time: Bt instances of the recipe of `monte_carlo_safety_rollouts` (same
+    task, same start states for the same seed, true plant), but every instance re-solves when its model says the last control stops
+    being safe, not every dt.  One EVENT is the control step with dt = 0 (solve only), the trigger step
+    (`ops.unicycle_trigger_step_prepare`: tau on the test grid around x, the control held for dt_b = min(clamp(tau, tau_min,
+    tau_max), horizon - t) on the plant, the instance's clock and the planner rows of its new time) and `ops.rollout_stats`.
+    The planner keeps its step-indexed definition: `dt` is ITS step, round(horizon / dt) rows, row min(floor(t / dt), P - 1) at
+    time t.  `max_events` iterations run with no device read (default ceil(horizon / tau_min), by which every instance is done).
+    Instances run on their own clocks; one that has reached `horizon` IDLES through the remaining iterations: its control step is
+    still solved (skipping it is not done here), its state, clock, event count and statistics no longer change.
+    gp: dict from BatchedControlAffineGP.as_dict() -- ls, sf, A, B of the bound are its ell, s2 (the output scale the reference
+    logs as knl_scalefactor), A, Bm -- or None: the fixed-kernel model, whose data kernel the bound needs from
+    trigger_hyper = dict(ls, sf, A, B) (one model or one per instance).  Any data kernel but RBF is refused.  Nte / off: the test
+    grid (`trigger_interval.default_test_grid`).  use_graph: capture one event and replay it (ignored with record).
+    Returns dict(stats (`reduce_rollout_stats`; mean_cost is per event), x_final, t[Bt], events[Bt], events_per_second[Bt] =
+    events / t, done = share of instances with t == horizon, dt_used = dict(min, median, max) over all events taken, min_h,
+    dist_to_goal, loop_seconds, task (the task tensors), and with record: rec = dict(x_before, u, status, tau, dt_used, t, x_after,
+    active, and what the solve of the event read and formed: plan, dot_plan, Mk, Bk) of [max_events, Bt, ...] tensors, `active`
+    telling which instances took that event (the rows of the others are stale)).
+    dt_used of every event is kept on the device ([max_events, Bt] in the working type) for the three figures."""
+    from . import trigger_interval as ti
+    dev = torch.device(device)
+    f = dict(dtype=dtype, device=dev)
+    if gp is not None:
+        ti._require_rbf(gp.get("kernel", "rbf"))
+        hyper = _trigger_hyper(gp["ell"], gp["s2"], gp["A"], gp["Bm"], Bt, f)
+    else:
+        if trigger_hyper is None or not {"ls", "sf", "A", "B"} <= set(trigger_hyper):
+            raise ValueError("self_triggered_rollouts: the fixed-kernel model has no data kernel of its own: pass "
+                             "trigger_hyper=dict(ls, sf, A, B)")
+        ti._require_rbf(trigger_hyper.get("kernel", "rbf"))
+        hyper = _trigger_hyper(trigger_hyper["ls"], trigger_hyper["sf"], trigger_hyper["A"], trigger_hyper["B"], Bt, f)
+    if not (0 < tau_min <= tau_max < math.inf) or not horizon > 0:
+        raise ValueError("self_triggered_rollouts: need 0 < tau_min <= tau_max < inf and horizon > 0")
+    numSteps = max(3, int(round(horizon / dt)))
+    if max_events is None:
+        max_events = int(math.ceil(horizon / tau_min))
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    x0, xg = torch.tensor(start, **f), torch.tensor(goal, **f)
+    task = unicycle_task_tensors(Bt, x0, xg, dtype, dev, max_risk=max_risk)
+    planner = PiecewiseLinearPlanner(x0, xg, numSteps, dt, frac_time_to_reach_goal=0.95)
+    x = (x0 + start_noise * torch.randn(Bt, 3, generator=gen, **f)).contiguous()
+    ws = ops.control_workspace(Bt, 2, dtype, dev)
+    tws = ops.trigger_workspace(Bt, dtype, dev)
+    if gp is None:
+        A = torch.diag(torch.tensor(kernel_diag_A, **f)).expand(Bt, 3, 3).contiguous()
+        ws["Mk"].zero_()
+        ws["Bk"].copy_(torch.eye(3, **f).expand(Bt, 3, 3))
+        gp = dict(A=A)
+    off_np = ti.default_test_grid(3, Nte) if off is None else (off.detach().cpu().numpy() if torch.is_tensor(off) else off)
+    r = ti._grid_norm(off_np)
+    off = torch.as_tensor(off_np).to(**f).contiguous()
+    plan_all = torch.stack([planner.plan(s).to(dtype=dtype) for s in range(numSteps)]).to(dev).contiguous()
+    dplan_all = torch.stack([planner.dot_plan(s).to(dtype=dtype) for s in range(numSteps)]).to(dev).contiguous()
+    task["plan"], task["dot_plan"] = plan_all[0].expand(Bt, 3).contiguous(), dplan_all[0].expand(Bt, 3).contiguous()
+    min_h = torch.full((Bt,), float("inf"), **f)
+    cost, cost_prev = torch.zeros(Bt, **f), torch.zeros(Bt, **f)
+    fails, fails_prev = (torch.zeros(Bt, dtype=torch.int32, device=dev) for _ in range(2))
+    active = torch.empty(Bt, dtype=torch.bool, device=dev)
+    dt_hist = torch.zeros(max_events, Bt, **f)
+    act_hist = torch.zeros(max_events, Bt, dtype=torch.bool, device=dev)
+    ectr = torch.zeros(1, dtype=torch.long, device=dev)
+    t, events = tws["t"], tws["events"]
+    solve = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=L_true, L_mean=L_mean, max_iters=max_iters)
+    trigger = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, dt, horizon, tau_min, tau_max,
+                                                L_true=L_true, deltaL=deltaL, zeta=zeta, L_alpha=L_alpha)
+    gam, w_cost = task["gammas"], task["w"]
+    state = [x, min_h, cost, fails, t, events, task["plan"], task["dot_plan"], dt_hist, act_hist, ectr]
+    rec = None
+    if record:
+        rec = dict(x_before=torch.empty(max_events, Bt, 3, **f), u=torch.empty(max_events, Bt, 2, **f),
+                   status=torch.empty(max_events, Bt, dtype=torch.int32, device=dev), tau=torch.empty(max_events, Bt, **f),
+                   dt_used=dt_hist, t=torch.empty(max_events, Bt, dtype=torch.float64, device=dev),
+                   x_after=torch.empty(max_events, Bt, 3, **f), active=act_hist, plan=torch.empty(max_events, Bt, 3, **f),
+                   dot_plan=torch.empty(max_events, Bt, 3, **f), Mk=torch.empty(max_events, Bt, 3, 3, **f),
+                   Bk=torch.empty(max_events, Bt, 3, 3, **f))
+
+    def one_event():
+        torch.lt(t, horizon, out=active)          # who takes this event (the trigger step leaves the others alone)
+        solve()                                   # rows -> terms -> SOCP at the current state, no plant
+        trigger()                                 # tau, the plant over the time the control is held, clock, planner rows
+        # the bookkeeping of `monte_carlo_safety_rollouts`, per event; an idle instance's cost and failure count are put back
+        # (its min_h cannot change: its state does not)
+        cost_prev.copy_(cost)
+        fails_prev.copy_(fails)
+        ops.rollout_stats(ws["cst"], ws["y"], ws["status"], w_cost, gam, min_h, cost, fails)
+        torch.where(active, cost, cost_prev, out=cost)
+        torch.where(active, fails, fails_prev, out=fails)
+        dt_hist.index_copy_(0, ectr, tws["dt_used"][None])
+        act_hist.index_copy_(0, ectr, active[None])
+        ectr.add_(1)
+
+    torch.cuda.synchronize(dev)
+    graph = None
+    if use_graph and not record:
+        side = torch.cuda.Stream(device=dev)
+        saved = [v.clone() for v in state]
+        with torch.cuda.stream(side):               # warm-up on the capture stream (allocator, lazy module load)
+            one_event()
+        side.synchronize()
+        for dst, src in zip(state, saved):
+            dst.copy_(src)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            one_event()
+        for dst, src in zip(state, saved):
+            dst.copy_(src)
+        torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter()
+    for e in range(max_events):
+        if graph is not None:
+            graph.replay()
+            continue
+        if record:
+            rec["x_before"][e], rec["plan"][e], rec["dot_plan"][e] = x, task["plan"], task["dot_plan"]
+        one_event()
+        if record:
+            rec["u"][e], rec["Mk"][e], rec["Bk"][e] = ws["y"][:, :2], ws["Mk"], ws["Bk"]
+            rec["status"][e] = ws["status"]
+            rec["tau"][e] = tws["tau"]
+            rec["t"][e] = t
+            rec["x_after"][e] = x
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter() - t_loop
+    collided = ~(min_h >= 0)
+    per_event_cost = cost / events.clamp(min=1).to(dtype)
+    stats = reduce_rollout_stats(collided.sum(), min_h.min(), per_event_cost.sum(), (fails > 0).sum(), Bt)
+    taken = dt_hist[act_hist]
+    dt_used = dict(min=float(taken.min()), median=float(taken.median()), max=float(taken.max())) if taken.numel() else None
+    out = dict(stats=stats, x_final=x, t=t, events=events, events_per_second=events.double() / t, done=float((t >= horizon).double().mean()),
+               dt_used=dt_used, min_h=min_h, dist_to_goal=(x[:, :2] - xg[:2]).norm(dim=1), loop_seconds=t_loop, task=task, rec=rec)
+    return out
+
+
 def online_pass_bytes(N, n, m, itemsize):
     """Algorithmic HBM bytes of ONE instance's append (+ control query) pass at N live points: the packed factor
     N(N+1)/2, the whitened targets and inputs N n each, the UH B rows N (1+m) -- read once -- and what the append writes:

@@ -166,6 +166,44 @@ int bcbf_trigger_interval_f64(const double* x, const double* off, const double* 
                               const double* uBu, const double* xvel, const double* Lh, double r, double deltaL, double zeta,
                               double L_alpha, double* Lkd, double* Lfh, double* tau, int B, int Bh, int Nte, int n, void* stream);
 
+/* One EVENT of the self-triggered closed loop for Bt unicycle instances in one launch: the trigger time of the control that
+ * bcbf_unicycle_control_step[_kind] called with dt = 0 (solve only, no plant) has just left in its workspace, and the plant step
+ * over that time -- the loop the paper prescribes, where the periodic loops re-solve every dt whatever the model says.  Every
+ * instance runs on its own clock t[b]; an instance with t[b] >= t_end is finished: nothing of it is read or written.  Else:
+ *   ubar = (1, u), u = y[b, 0:2];   uBu = ubar' Bhyp ubar;   xvel = |fhat + ghat u + M_k ubar|  (the model's one-step prediction
+ *   over dt, the xtp1 the logging loop records; M_k ubar formed as bcbf_unicycle_control_step_sampled forms it);
+ *   Lh   = the largest single element of ObstacleCBF.grad_cbf over the test points off[Nte,3] + x[b], the Kob obstacles and the
+ *          three components, rho^2 of an obstacle being the SUM over all test points of |p_a - c_k|^2 as the reference's
+ *          batch-wide torch.norm takes it (unicycle_move_to_pose.py:670; trigger_interval.py:159);
+ *   Lkd, Lfh, tau as bcbf_trigger_interval computes them from these three, each rounded to the working type first (n = 3);
+ *   solved (status[b] == BCBF_SOCP_OPTIMAL):  hold = clamp(tau, tau_min, tau_max), tau = +inf giving tau_max and NaN or
+ *          tau <= 0 giving tau_min;  dt_b = min(hold, t_end - t[b]);  x[b] += g(x; L_true) u dt_b, the arithmetic of bcbf_unicycle_step;
+ *   unsolved: the state is kept and dt_b = min(tau_max, t_end - t[b]), as the periodic loop lets time pass;
+ *   t[b] += dt_b (the last, partial step lands on t_end itself), events[b] += 1, and the planner's rows of index
+ *   min(floor(t[b] / dt_plan), P - 1) are copied from plan_all[P,3], dplan_all[P,3] into plan[b], dot_plan[b] for the next solve.
+ * x, t (fp64 in both precisions), events (int32), plan, dot_plan are in/out; y, status, fhat[Bt,3], ghat[Bt,3,2], Mk[Bt,3,3] are
+ * the control step's; centers[Bt,Kob,2], tw[2] the obstacles'; ls[Bh,3], sf[Bh], Adiag[Bh,3], Bhyp[Bh,3,3] the kernel's
+ * hyper-parameters with Bh = Bt or 1; r = the reference's pdist(grid) scalar.  Outputs, each may be NULL: tau[Bt] (raw, before
+ * the clamp), dt_used[Bt], Lfh[Bt], Lkd[Bt,3], Lh[Bt], xvel[Bt], uBu[Bt].  One workgroup per instance, the points in LDS as in
+ * bcbf_trigger_interval; the block sum and maximum of Lh by shuffles and LDS, no atomics.
+ * Limits: Bt >= 1, Bh in {1, Bt}, 1 <= Kob < BCBF_MAX_CONSTRAINTS, 1 <= Nte with 16 Nte sizeof(T) / 4 <= 160 KB - 256 B, P >= 1,
+ * dt_plan > 0, 0 < tau_min <= tau_max < inf, every pointer but the seven outputs non-NULL; otherwise BCBF_EINVAL before any HIP
+ * call, reason in bcbf_last_error.  No allocation, no host synchronisation: capturable. */
+int bcbf_unicycle_trigger_step_f32(float* x, const float* y, const int* status, const float* fhat, const float* ghat, const float* Mk,
+                                   const float* centers, const float* tw, const float* off, double r, const float* ls, const float* sf,
+                                   const float* Adiag, const float* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min,
+                                   double tau_max, double t_end, float L_true, const float* plan_all, const float* dplan_all,
+                                   double dt_plan, double* t, int* events, float* plan, float* dot_plan, float* tau, float* dt_used,
+                                   float* Lfh, float* Lkd, float* Lh, float* xvel, float* uBu, int Bt, int Bh, int Kob, int Nte, int P,
+                                   void* stream);
+int bcbf_unicycle_trigger_step_f64(double* x, const double* y, const int* status, const double* fhat, const double* ghat,
+                                   const double* Mk, const double* centers, const double* tw, const double* off, double r,
+                                   const double* ls, const double* sf, const double* Adiag, const double* Bhyp, double deltaL, double zeta,
+                                   double L_alpha, double tau_min, double tau_max, double t_end, double L_true, const double* plan_all,
+                                   const double* dplan_all, double dt_plan, double* t, int* events, double* plan, double* dot_plan,
+                                   double* tau, double* dt_used, double* Lfh, double* Lkd, double* Lh, double* xvel, double* uBu, int Bt,
+                                   int Bh, int Kob, int Nte, int P, void* stream);
+
 /* K2 on a caller-supplied dense SPD matrix (lower triangle of Kb[Bt,N,N] is read): same outputs.
  * Replaces torch.linalg.cholesky (control_affine_model.py:911). */
 int bcbf_potrf_f32(const float* Kb, float* Lop, float* Ldense, int* info, int Bt, int N, void* stream);

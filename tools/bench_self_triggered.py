@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""Time one event of the self-triggered loop: the fused trigger step (bcbf_unicycle_trigger_step) against today's sequence on the
+same inputs -- the model's one-step prediction in torch, `trigger_interval_batch` (uBu, xvel, Lh in torch, then
+bcbf_trigger_interval) and `bcbf_unicycle_step` -- at Bt = 4096, Nte = 729, fp32 and fp64; then one whole event (control step with
+dt = 0, trigger step, bcbf_rollout_stats), eager and replayed from a captured graph.
+
+    python tools/bench_self_triggered.py [--B 4096] [--Nte 729] [--out profiles/self_triggered.json]
+
+Fixed-kernel model of the Monte-Carlo recipe, start states of `monte_carlo_safety_rollouts`.  Both forms' tau are compared before
+anything is timed.  The sequence cannot hold every instance's control for its OWN time (bcbf_unicycle_step takes one dt for the
+batch): it is timed with one dt, which flatters it.  tau_max = 1e-6 keeps the state where it is over the timed repetitions, so
+every repetition of either form sees the same inputs to six digits.  HIP events around back-to-back calls after a warm-up that
+raises the clocks (tools/_timing.py); the fused step, the sequence and the pair kernel alone are timed three times in alternation and
+the medians reported (all nine figures are kept)."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from _timing import timeit  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=4096)
+    ap.add_argument("--Nte", type=float, default=1e3, help="rounded down to a cube, as the reference does (1e3 -> 729)")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "self_triggered.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_self_triggered needs the GPU: nothing is measured without it")
+    from bayesian_cbf_amd import ops
+    from bayesian_cbf_amd import trigger_interval as ti
+    from bayesian_cbf_amd.rollouts import _trigger_hyper, unicycle_task_tensors
+    from bayesian_cbf_amd.unicycle_move_to_pose import ObstacleCBF
+    grid = ti.default_test_grid(3, args.Nte)
+    Nte, Bt = grid.shape[0], args.B
+    r = ti._grid_norm(grid)
+    res = dict(B=Bt, Nte=Nte, device=torch.cuda.get_device_name(0), reps=args.reps,
+               pair_part_alone_ms_f32_recorded=0.372)            # profiles/trigger_interval.json, the only figure measured before
+    L_true, L_mean, dt_ref = 12.0, 1.0, 0.01
+    for dtype, name in ((torch.float32, "f32"), (torch.float64, "f64")):
+        f = dict(dtype=dtype, device="cuda")
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        x0, xg = torch.tensor([-3.0, -1.0, -math.pi / 4], **f), torch.tensor([0.0, 0.0, math.pi / 4], **f)
+        task = unicycle_task_tensors(Bt, x0, xg, dtype, torch.device("cuda"))
+        x = (x0 + 0.05 * torch.randn(Bt, 3, generator=gen, **f)).contiguous()
+        task["plan"] = (x0 + 0.1 * (xg - x0)).expand(Bt, 3).contiguous()
+        task["dot_plan"] = ((xg - x0) / 10.0).expand(Bt, 3).contiguous()
+        ws = ops.control_workspace(Bt, 2, dtype, "cuda")
+        ws["Mk"].zero_()
+        ws["Bk"].copy_(torch.eye(3, **f).expand(Bt, 3, 3))
+        gp = dict(A=(1e-2 * torch.eye(3, **f)).expand(Bt, 3, 3).contiguous())
+        solve = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=L_true, L_mean=L_mean, max_iters=30)
+        solve()
+        ls = 0.05 + 0.1 * torch.rand(Bt, 3, generator=gen, **f)
+        sf = 0.5 + torch.rand(Bt, generator=gen, **f)
+        A = torch.diag_embed(1e-2 * (0.5 + torch.rand(Bt, 3, generator=gen, **f)))
+        Bh = torch.eye(3, **f).expand(Bt, 3, 3) * (0.5 + torch.rand(Bt, 1, 1, generator=gen, **f))
+        hyper = _trigger_hyper(ls, sf, A, Bh, Bt, f)
+        off = torch.as_tensor(grid, **f).contiguous()
+        tws = ops.trigger_workspace(Bt, dtype, "cuda")
+        P = 200
+        plan_all, dplan_all = task["plan"][:1].expand(P, 3).contiguous(), task["dot_plan"][:1].expand(P, 3).contiguous()
+        fused = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, 0.05, 1e9, 1e-9, 1e-6,
+                                                  L_true=L_true)
+        cbfs = [ObstacleCBF(task["centers"][:, k], task["radii"][:, k], (0.7, 0.3)) for k in range(2)]
+        x_seq = x.clone()
+        u = ws["y"][:, :2].contiguous()
+
+        def sequence():
+            ub = torch.cat([torch.ones(Bt, 1, **f), u], dim=1)
+            xtp1 = x_seq + (ws["fhat"] + torch.einsum("bdi,bi->bd", ws["ghat"], u) + torch.einsum("bdc,bc->bd", ws["Mk"], ub)) * dt_ref
+            out = ti.trigger_interval_batch(x_seq, xtp1, u, ls, sf, A, Bh, cbfs, dt_ref, off=off, r=r)
+            ops.unicycle_step(x_seq, u, 1e-6, L_true)
+            return out
+
+        # the same numbers first
+        fused()
+        seq = sequence()
+        torch.cuda.synchronize()
+        ok = ws["status"] == 0
+        dev = float(((tws["tau"] - seq["tau"]).abs() / seq["tau"].abs())[ok].max())
+        pair = lambda: ops.trigger_interval(x_seq, off, ls, sf, hyper["Adiag"], seq["uBu"], seq["xvel"], seq["Lh"], r)
+        runs = [[timeit(fn, reps=args.reps) for fn in (fused, sequence, pair)] for _ in range(3)]      # alternating; the medians count
+        fused_ms, seq_ms, pair_ms = (sorted(col)[1] for col in zip(*runs))
+        # one whole event
+        min_h, cost = torch.full((Bt,), float("inf"), **f), torch.zeros(Bt, **f)
+        fails = torch.zeros(Bt, dtype=torch.int32, device="cuda")
+
+        def event():
+            solve()
+            fused()
+            ops.rollout_stats(ws["cst"], ws["y"], ws["status"], task["w"], task["gammas"], min_h, cost, fails)
+
+        solve_ms = timeit(solve, reps=args.reps)
+        eager_ms = timeit(event, reps=args.reps)
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            event()
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            event()
+        torch.cuda.synchronize()
+        graph_ms = timeit(graph.replay, reps=args.reps)
+        res[name] = dict(fused_trigger_step_ms=fused_ms, sequence_ms=seq_ms, sequence_over_fused=seq_ms / fused_ms,
+                         pair_kernel_alone_ms=pair_ms, fused_over_pair_kernel_alone=fused_ms / pair_ms, tau_max_rel_dev_vs_sequence=dev,
+                         solved=int(ok.sum()), control_step_dt0_ms=solve_ms, event_eager_ms=eager_ms, event_graph_ms=graph_ms,
+                         events_per_s_graph=Bt / (graph_ms * 1e-3), fused_is_faster_than_sequence=bool(fused_ms < seq_ms),
+                         alternating_runs_ms=dict(fused=[q[0] for q in runs], sequence=[q[1] for q in runs], pair_kernel=[q[2] for q in runs]))
+        print(json.dumps({name: res[name]}))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
