@@ -17,6 +17,17 @@
 // bcbf_trigger_interval fed the same three numbers.  Thread 0 then acts: clamp, Euler step of the true plant (the arithmetic of
 // bcbf_unicycle_step), the instance's clock, its event count and the planner rows of its new time.  An instance whose clock has
 // reached t_end leaves before anything is read or written.
+//
+// bcbf_unicycle_trigger_step_audit is the same launch with two optional pieces of work for thread 0, in fp64 from the values as the
+// working type stores them, every output rounded once (the second instantiation of trigger_step_body; the plain entry's code is
+// the first and does not change with it):
+//   the plant drawn from the posterior (z given): a solved instance moves by xdot_s = fhat + ghat u + M_k ubar +
+//     sqrt(max(ubar' B_k ubar, 0)) L_A z held for dt_b -- the arithmetic of the sampled branch of socp_quad_kernel, which does
+//     nothing when the solve is called with dt = 0 -- with the risk bookkeeping of rollout_risk_kernel (unicycle.hip), done here
+//     because that kernel cannot tell an idle instance from a live one;
+//   the audit of the held control (u_held given): the two sides of every obstacle row's cone, mean >= rho std, evaluated with
+//     the control of the instance's PREVIOUS event on the rows the solve of this event wrote at the state where that control is
+//     released -- what tau promised, measured one launch later.
 #include "trigger_pairs.h"
 #include <stdio.h>
 
@@ -35,6 +46,16 @@ struct TriggerStepArgs {
     int per_instance_hyper, Kob, Nte, P;
 };
 
+// what bcbf_unicycle_trigger_step_audit adds to the arguments: the rows of the solve, the posterior plant (z == nullptr: the true
+// plant) and the audit of the held control (u_held == nullptr: none)
+template <typename T>
+struct TriggerAuditArgs {
+    const T* Bk; const T* A; const T* grad; const T* cst; const T* sign; const T* rho;
+    const T* z; T* xdot_s; T* cbc_s; int* viol; int* solved; T* min_cbc;
+    T* u_held; int* held; T* held_mean; T* held_margin; int* audit_n; int* audit_neg; T* audit_min;
+};
+struct TriggerNoAudit {};
+
 // sum or maximum of v over the workgroup, through red[slot] (every slot is used once per launch: no barrier after the read)
 __device__ inline double block_reduce(double v, double (*red)[TI_WAVES], int slot, bool is_max) {
 #pragma unroll
@@ -49,8 +70,122 @@ __device__ inline double block_reduce(double v, double (*red)[TI_WAVES], int slo
     return out;
 }
 
+// fhat + ghat u + M_k ubar of instance b, u = (ub[1], ub[2]), component d, as the sampled branch of socp_quad_kernel forms it
 template <typename T>
-__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const TriggerStepArgs<T> a) {
+__device__ inline double model_velocity(const TriggerStepArgs<T>& a, int b, int d, const double (&ub)[3]) {
+    const T* g = a.ghat + ((size_t)b * 3 + d) * 2;
+    const T* M = a.Mk + ((size_t)b * 3 + d) * 3;
+    const double gu = (double)g[0] * ub[1] + (double)g[1] * ub[2];
+    const double mu = (double)M[0] + (double)M[1] * ub[1] + (double)M[2] * ub[2];
+    return (double)a.fhat[(size_t)b * 3 + d] + gu + mu;
+}
+
+// c as the counters see it: NaN is below everything (it counts as negative and takes the minimum)
+template <typename T> __device__ inline T nan_is_lowest(T c) { return c == c ? c : T(-INFINITY); }
+
+// The audit of the held control (one thread): mean_k, margin_k = mean_k - rho std_k of the obstacle rows for ubar_h = (1, u_held)
+template <typename T>
+__device__ inline void audit_held_control(const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, int b) {
+    const double ub[3] = {1.0, (double)q.u_held[(size_t)b * 2], (double)q.u_held[(size_t)b * 2 + 1]};
+    const T* Bk = q.Bk + (size_t)b * 9;
+    const T* A = q.A + (size_t)b * 9;
+    double s = 0.0, m[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s += ub[i] * (double)Bk[i * 3 + c] * ub[c];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) m[d] = model_velocity<T>(a, b, d, ub);
+    const double rho = (double)q.rho[b];
+    for (int k = 1; k <= a.Kob; ++k) {
+        const T* gr = q.grad + ((size_t)b * (1 + a.Kob) + k) * 3;
+        const double g[3] = {(double)gr[0], (double)gr[1], (double)gr[2]};
+        double gAg = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gAg += g[i] * (double)A[i * 3 + c] * g[c];
+        const double mean = (double)q.sign[k] * (g[0] * m[0] + g[1] * m[1] + g[2] * m[2] + (double)q.cst[(size_t)b * (1 + a.Kob) + k]);
+        const double margin = mean - rho * sqrt(fmax(s * gAg, 0.0));
+        const size_t o = (size_t)b * a.Kob + k - 1;
+        const T v[2] = {(T)mean, (T)margin};           // the counters see what is stored
+        q.held_mean[o] = v[0];
+        q.held_margin[o] = v[1];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            q.audit_neg[o * 2 + j] += v[j] >= T(0) ? 0 : 1;
+            const T c = nan_is_lowest(v[j]), mn = q.audit_min[o * 2 + j];
+            q.audit_min[o * 2 + j] = c < mn ? c : mn;
+        }
+    }
+    q.audit_n[b] += 1;
+}
+
+// The plant drawn from the posterior over the hold dt (one thread): x, xdot_s, cbc_s and the risk counters of instance b
+template <typename T>
+__device__ inline void posterior_plant_step(const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, int b, const T (&xb)[3], T u0,
+                                            T u1, bool solved, T dt) {
+    const int K = 1 + a.Kob;
+    double xd[3] = {0.0, 0.0, 0.0};
+    if (solved) {
+        const double ub[3] = {1.0, (double)u0, (double)u1};
+        const T* Bk = q.Bk + (size_t)b * 9;
+        const T* A = q.A + (size_t)b * 9;
+        double s_ = 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s_ += ub[i] * (double)Bk[i * 3 + c] * ub[c];
+        const double rs = __builtin_sqrt(fmax(s_, 0.0));
+        double LA[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double d = (double)A[j * 3 + j];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) if (p < j) d -= LA[j][p] * LA[j][p];
+            if (d > 0.0) {                           // (else: the column stays zero)
+                const double ljj = __builtin_sqrt(d);
+                LA[j][j] = ljj;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) if (i > j) {
+                    double v = (double)A[i * 3 + j];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) if (p < j) v -= LA[i][p] * LA[j][p];
+                    LA[i][j] = v / ljj;
+                }
+            }
+        }
+        const double z0 = (double)q.z[(size_t)b * 3], z1 = (double)q.z[(size_t)b * 3 + 1], z2 = (double)q.z[(size_t)b * 3 + 2];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            xd[d] = model_velocity<T>(a, b, d, ub) + rs * (LA[d][0] * z0 + LA[d][1] * z1 + LA[d][2] * z2);
+            a.x[(size_t)b * 3 + d] = (T)((double)xb[d] + xd[d] * (double)dt);
+        }
+        if (q.solved) q.solved[b] += 1;
+    }
+    if (q.xdot_s) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) q.xdot_s[(size_t)b * 3 + d] = (T)xd[d];
+    }
+    for (int k = 0; k < K; ++k) {
+        T cb = T(0);
+        if (solved) {
+            const T* gr = q.grad + ((size_t)b * K + k) * 3;
+            cb = (T)((double)q.sign[k] * ((double)gr[0] * xd[0] + (double)gr[1] * xd[1] + (double)gr[2] * xd[2] + (double)q.cst[(size_t)b * K + k]));
+        }
+        if (q.cbc_s) q.cbc_s[(size_t)b * K + k] = cb;
+        if (solved && k > 0 && q.solved) {           // rollout_risk_kernel's bookkeeping: a non-finite value is a violation
+            const size_t o = (size_t)b * a.Kob + k - 1;
+            const T c = cb - cb == T(0) ? cb : T(-INFINITY), mn = q.min_cbc[o];
+            q.viol[o] += c < T(0) ? 1 : 0;
+            q.min_cbc[o] = c < mn ? c : mn;
+        }
+    }
+}
+
+// The event of one instance by its workgroup.  AUDIT = false, Q = TriggerNoAudit: bcbf_unicycle_trigger_step.
+template <typename T, bool AUDIT, typename Q>
+__device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, const Q& au) {
     constexpr int NS = 3, ST = ti_stride(NS);
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_raw[];
     __shared__ T ts_red[TI_WAVES][NS];
@@ -132,7 +267,21 @@ __global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const
     if (solved) hold = !(tq > 0.0) ? a.tau_min : fmin(fmax(tq, a.tau_min), a.tau_max);
     const bool last = !(hold < left);
     const T dtT = (T)(last ? left : hold);
-    if (solved) {                                     // ... the plant over it
+    bool euler = solved;
+    if constexpr (AUDIT) {
+        // what the last control does at the state where it is released, on this event's rows, before anything of the event
+        if (au.u_held != nullptr && au.held[b] != 0) audit_held_control<T>(a, au, b);
+        if (au.z != nullptr) {                         // ... the plant drawn from the posterior over it
+            euler = false;
+            posterior_plant_step<T>(a, au, b, xb, u0, u1, solved, dtT);
+        }
+        if (au.u_held != nullptr) {
+            au.u_held[(size_t)b * 2] = u0;
+            au.u_held[(size_t)b * 2 + 1] = u1;
+            au.held[b] = solved ? 1 : 0;
+        }
+    }
+    if (euler) {                                      // ... the plant over it
         const T th = xb[2];
         a.x[(size_t)b * 3] = xb[0] + cos(th) * u0 * dtT;
         a.x[(size_t)b * 3 + 1] = xb[1] + sin(th) * u0 * dtT;
@@ -150,6 +299,16 @@ __global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const
         a.plan[(size_t)b * 3 + j] = a.plan_all[(size_t)row * 3 + j];
         a.dot_plan[(size_t)b * 3 + j] = a.dplan_all[(size_t)row * 3 + j];
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const TriggerStepArgs<T> a) {
+    trigger_step_body<T, false>(a, TriggerNoAudit{});
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_audit_kernel(const TriggerStepArgs<T> a, const TriggerAuditArgs<T> q) {
+    trigger_step_body<T, true>(a, q);
 }
 
 template <typename T>
@@ -189,6 +348,37 @@ static int launch_trigger_step(const char* entry, TriggerStepArgs<T> a, int Bt, 
     return check_launch(entry);
 }
 
+template <typename T>
+static int trigger_audit_args_ok(const char* entry, const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, int Bt, int Bh) {
+    if (!trigger_step_args_ok<T>(entry, a, Bt, Bh)) return 0;
+    static thread_local char msg[280];
+    const int counters = (q.viol != nullptr) + (q.solved != nullptr) + (q.min_cbc != nullptr);
+    const int held = (q.u_held != nullptr) + (q.held != nullptr) + (q.held_mean != nullptr) + (q.held_margin != nullptr) +
+                     (q.audit_n != nullptr) + (q.audit_neg != nullptr) + (q.audit_min != nullptr);
+    const char* why = nullptr;
+    if (!q.Bk || !q.A || !q.grad || !q.cst || !q.sign || !q.rho) why = "null row of the solve (Bk, A, grad, cst, sign, rho)";
+    else if (a.Kob + 1 > BCBF_MAX_QUAD_CONSTRAINTS) why = "need Kob + 1 <= BCBF_MAX_QUAD_CONSTRAINTS (the rows are the fused solve's)";
+    else if (counters != 0 && counters != 3) why = "the risk counters (viol, solved, min_cbc) are given together or not at all";
+    else if (!q.z && (q.xdot_s || q.cbc_s || counters)) why = "xdot_s, cbc_s and the risk counters need the draws z";
+    else if (held != 0 && held != 7)
+        why = "the audit buffers (u_held, held, held_mean, held_margin, audit_n, audit_neg, audit_min) are given together or not at all";
+    if (!why) return 1;
+    snprintf(msg, sizeof(msg), "%s: %s (Bt=%d Kob=%d counters=%d/3 audit=%d/7)", entry, why, Bt, a.Kob, counters, held);
+    set_error_message(msg);
+    return 0;
+}
+
+template <typename T>
+static int launch_trigger_step_audit(const char* entry, TriggerStepArgs<T> a, const TriggerAuditArgs<T>& q, int Bt, int Bh, void* stream) {
+    if (!trigger_audit_args_ok<T>(entry, a, q, Bt, Bh)) return BCBF_EINVAL;
+    a.per_instance_hyper = Bh == Bt && Bt > 1 ? 1 : 0;
+    const size_t lds = (size_t)a.Nte * ti_stride(3) * sizeof(T);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_audit_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((unicycle_trigger_step_audit_kernel<T>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a, q);
+    return check_launch(entry);
+}
+
 }  // namespace bcbf
 
 #define BCBF_TRIGGER_STEP(T, SUF)                                                                                                 \
@@ -205,3 +395,23 @@ static int launch_trigger_step(const char* entry, TriggerStepArgs<T> a, int Bt, 
 BCBF_TRIGGER_STEP(float, f32)
 BCBF_TRIGGER_STEP(double, f64)
 #undef BCBF_TRIGGER_STEP
+
+#define BCBF_TRIGGER_STEP_AUDIT(T, SUF)                                                                                           \
+    extern "C" int bcbf_unicycle_trigger_step_audit_##SUF(                                                                        \
+        T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off, \
+        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, \
+        double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, int* events, T* plan, \
+        T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu, const T* Bk, const T* A, const T* grad, const T* cst, \
+        const T* sign, const T* rho, const T* z, T* xdot_s, T* cbc_s, int* viol, int* solved, T* min_cbc, T* u_held, int* held,   \
+        T* held_mean, T* held_margin, int* audit_n, int* audit_neg, T* audit_min, int Bt, int Bh, int Kob, int Nte, int P,         \
+        void* stream) {                                                                                                           \
+        bcbf::TriggerStepArgs<T> a = {x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, \
+                                      tau_min, tau_max, t_end, L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, \
+                                      dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P};                                          \
+        const bcbf::TriggerAuditArgs<T> q = {Bk, A, grad, cst, sign, rho, z, xdot_s, cbc_s, viol, solved, min_cbc, u_held, held,  \
+                                             held_mean, held_margin, audit_n, audit_neg, audit_min};                              \
+        return bcbf::launch_trigger_step_audit<T>("bcbf_unicycle_trigger_step_audit_" #SUF, a, q, Bt, Bh, stream);                \
+    }
+BCBF_TRIGGER_STEP_AUDIT(float, f32)
+BCBF_TRIGGER_STEP_AUDIT(double, f64)
+#undef BCBF_TRIGGER_STEP_AUDIT

@@ -1416,8 +1416,74 @@ def trigger_workspace(Bt, dtype, device):
     return ws
 
 
+def trigger_audit_workspace(Bt, Kob, dtype, device):
+    """Buffers of `unicycle_trigger_step_prepare(sampled=..., audit=...)` (bcbf_unicycle_trigger_step_audit), as
+    dict(sampled=dict(z[Bt,3], xdot_s[Bt,3], cbc_s[Bt,1+Kob], viol[Bt,Kob], solved[Bt], min_cbc[Bt,Kob]),
+    audit=dict(u_held[Bt,2], held[Bt], held_mean[Bt,Kob], held_margin[Bt,Kob], audit_n[Bt], audit_neg[Bt,Kob,2],
+    audit_min[Bt,Kob,2])): the two dicts that call takes.  Counters and flags (int32) are zero, the running minima +inf; `z`
+    is the caller's to refill with standard normals before every event (the library draws no random numbers)."""
+    f = dict(dtype=dtype, device=device)
+    i = dict(dtype=torch.int32, device=device)
+    sampled = dict(z=torch.zeros(Bt, 3, **f), xdot_s=torch.zeros(Bt, 3, **f), cbc_s=torch.zeros(Bt, 1 + Kob, **f),
+                   viol=torch.zeros(Bt, Kob, **i), solved=torch.zeros(Bt, **i), min_cbc=torch.full((Bt, Kob), float("inf"), **f))
+    audit = dict(u_held=torch.zeros(Bt, 2, **f), held=torch.zeros(Bt, **i), held_mean=torch.zeros(Bt, Kob, **f),
+                 held_margin=torch.zeros(Bt, Kob, **f), audit_n=torch.zeros(Bt, **i), audit_neg=torch.zeros(Bt, Kob, 2, **i),
+                 audit_min=torch.full((Bt, Kob, 2), float("inf"), **f))
+    return dict(sampled=sampled, audit=audit)
+
+
+_TRIGGER_SAMPLED_KEYS = ("z", "xdot_s", "cbc_s", "viol", "solved", "min_cbc")
+_TRIGGER_AUDIT_KEYS = ("u_held", "held", "held_mean", "held_margin", "audit_n", "audit_neg", "audit_min")
+
+
+def _trigger_audit_check(task, ws, x, gp_A, sampled, audit):
+    """Shape and dtype checks (ValueError) of what bcbf_unicycle_trigger_step_audit takes beyond the plain entry; returns the
+    tensors in the entry's order: [Bk, A, grad, cst, sign, rho], the six of `sampled`, the seven of `audit` (None where absent)."""
+    Bt, Kob = x.shape[0], task["centers"].shape[1]
+    if gp_A is None:
+        raise ValueError("trigger step: sampled / audit need gp_A, the kernel matrix A[Bt,3,3] (or [1,3,3]) the solve ran with")
+    if gp_A.dim() != 3 or tuple(gp_A.shape[1:]) != (3, 3) or gp_A.shape[0] not in (1, Bt):
+        raise ValueError("trigger step: gp_A %s must be [Bt, 3, 3] or [1, 3, 3]" % (tuple(gp_A.shape),))
+    A = gp_A if gp_A.shape[0] == Bt else gp_A.expand(Bt, 3, 3).contiguous()
+    for k, shape in dict(Bk=(Bt, 3, 3), grad=(Bt, 1 + Kob, 3), cst=(Bt, 1 + Kob)).items():
+        if tuple(ws[k].shape) != shape:
+            raise ValueError("trigger step: ws[%r] %s must be %s" % (k, tuple(ws[k].shape), shape))
+    if tuple(task["sign"].shape) != (1 + Kob,) or tuple(task["rho"].shape) != (Bt,):
+        raise ValueError("trigger step: task['sign'] must be [1+Kob] and task['rho'] [Bt]")
+    ints = ("viol", "solved", "held", "audit_n", "audit_neg")
+
+    def group(d, keys, shapes, required, name):
+        if d is None:
+            return [None] * len(keys)
+        unknown = set(d) - set(keys)
+        if unknown:
+            raise ValueError("trigger step: %s has no buffer %s" % (name, sorted(unknown)))
+        out = []
+        for k in keys:
+            v = d.get(k)
+            if v is None:
+                if k in required:
+                    raise ValueError("trigger step: %s[%r] is required" % (name, k))
+            else:
+                want = torch.int32 if k in ints else x.dtype
+                if v.dtype != want or not v.is_contiguous() or tuple(v.shape) != shapes[k]:
+                    raise ValueError("trigger step: %s[%r] (%s %s) must be a contiguous %s tensor of shape %s"
+                                     % (name, k, v.dtype, tuple(v.shape), want, shapes[k]))
+            out.append(v)
+        return out
+
+    s_shapes = dict(z=(Bt, 3), xdot_s=(Bt, 3), cbc_s=(Bt, 1 + Kob), viol=(Bt, Kob), solved=(Bt,), min_cbc=(Bt, Kob))
+    a_shapes = dict(u_held=(Bt, 2), held=(Bt,), held_mean=(Bt, Kob), held_margin=(Bt, Kob), audit_n=(Bt,), audit_neg=(Bt, Kob, 2),
+                    audit_min=(Bt, Kob, 2))
+    sv = group(sampled, _TRIGGER_SAMPLED_KEYS, s_shapes, ("z",), "sampled")
+    if len({v is None for v in sv[3:]}) != 1:
+        raise ValueError("trigger step: sampled['viol'], ['solved'], ['min_cbc'] are given together or not at all")
+    av = group(audit, _TRIGGER_AUDIT_KEYS, a_shapes, _TRIGGER_AUDIT_KEYS, "audit")
+    return [ws["Bk"], A, ws["grad"], ws["cst"], task["sign"], task["rho"]] + sv + av
+
+
 def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, dt_plan, t_end, tau_min, tau_max,
-                                  L_true=1.0, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, stream=None):
+                                  L_true=1.0, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, stream=None, gp_A=None, sampled=None, audit=None):
     """Bind the buffers of one EVENT of the self-triggered loop once and return `step()` (bcbf_unicycle_trigger_step, one launch):
     run it after the `step()` of `unicycle_control_step_prepare(..., dt=0)` on the same task / ws / x.  It computes the trigger
     time tau of the control in ws['y'] (uBu, xvel, Lh, Lkd, Lfh, tau as `trigger_interval.trigger_interval_batch` does, on the test
@@ -1425,9 +1491,22 @@ def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dpl
     instances keep their state and let min(tau_max, t_end - t) pass), advances tws['t'], tws['events'] and copies the planner rows
     of the new time, min(floor(t / dt_plan), P - 1) of plan_all[P,3] / dplan_all[P,3], into task['plan'], task['dot_plan'].
     Instances with t >= t_end are left alone.  hyper = dict(ls[Bh,3], sf[Bh], Adiag[Bh,3], B[Bh,3,3]), Bh = Bt or 1; r = pdist(off)
-    (`trigger_interval._grid_norm`); tws from `trigger_workspace`.  The tensors must keep their storage; the closure keeps them."""
+    (`trigger_interval._grid_norm`); tws from `trigger_workspace`.  The tensors must keep their storage; the closure keeps them.
+    sampled / audit (dicts from `trigger_audit_workspace`; either, both or neither) bind bcbf_unicycle_trigger_step_audit instead,
+    which also reads the rows of the FUSED solve in ws (Bk, grad, cst), task['sign'], task['rho'] and gp_A, the kernel matrix
+    A[Bt,3,3] or [1,3,3] that solve ran with:
+    sampled = dict(z[Bt,3], xdot_s | None, cbc_s | None, and viol, solved, min_cbc together | None): the control is held on a
+    plant DRAWN FROM THE MODEL'S POSTERIOR, xdot_s = fhat + ghat u + M_k ubar + sqrt(ubar' B_k ubar) chol(A) z (L_true is ignored),
+    cbc_s = sign_k (grad_k . xdot_s + cst_k), and the risk counters of `rollout_risk` are kept for the instances that took the event;
+    refill `z` in place before every event.
+    audit = dict(u_held, held, held_mean, held_margin, audit_n, audit_neg, audit_min), all seven: where the instance's previous
+    event was solved, the mean and the margin mean - rho std of every obstacle row's condition under the control of THAT event,
+    on this event's rows (the state where the control is released), with counts of negative values and running minima.
+    With neither it is the plain entry, unchanged."""
     Bt = x.shape[0]
+    more = _trigger_audit_check(task, ws, x, gp_A, sampled, audit) if (sampled is not None or audit is not None) else []
     ls, sf, Adiag, Bh_ = hyper["ls"], hyper["sf"], hyper["Adiag"], hyper["B"]
+    _chk(x, *more)
     _chk(x, off, ls, sf, Adiag, Bh_, plan_all, dplan_all, task["plan"], task["dot_plan"], task["centers"], task["tw"], ws["y"],
          ws["fhat"], ws["ghat"], ws["Mk"], tws["tau"], tws["dt_used"], tws["Lfh"], tws["Lkd"], tws["Lh"], tws["xvel"], tws["uBu"])
     if x.dim() != 2 or x.shape[1] != 3 or off.dim() != 2 or off.shape[1] != 3:
@@ -1449,20 +1528,22 @@ def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dpl
     for k in ("tau", "dt_used", "Lfh", "Lh", "xvel", "uBu", "Lkd"):
         if tuple(tws[k].shape) != ((Bt, 3) if k == "Lkd" else (Bt,)):
             raise ValueError("trigger step: output buffer %s of the wrong shape" % k)
-    fn = getattr(lib, "bcbf_unicycle_trigger_step" + _suf(x))
+    entry = "bcbf_unicycle_trigger_step_audit" if more else "bcbf_unicycle_trigger_step"
+    tail, keep_more = tuple(_p(v) for v in more), (tuple(more),)
+    fn = getattr(lib, entry + _suf(x))
     args = (_p(x), _p(ws["y"]), _p(ws["status"]), _p(ws["fhat"]), _p(ws["ghat"]), _p(ws["Mk"]), _p(task["centers"]), _p(task["tw"]),
             _p(off), float(r), _p(ls), _p(sf), _p(Adiag), _p(Bh_), float(deltaL), float(zeta), float(L_alpha), float(tau_min),
             float(tau_max), float(t_end), float(L_true), _p(plan_all), _p(dplan_all), float(dt_plan), _p(t), _p(events),
             _p(task["plan"]), _p(task["dot_plan"]), _p(tws["tau"]), _p(tws["dt_used"]), _p(tws["Lfh"]), _p(tws["Lkd"]), _p(tws["Lh"]),
-            _p(tws["xvel"]), _p(tws["uBu"]), Bt, Bh, Kob, off.shape[0], P)
-    keep = (dict(task), dict(ws), dict(tws), x, off, dict(hyper), plan_all, dplan_all, stream)
+            _p(tws["xvel"]), _p(tws["uBu"])) + tail + (Bt, Bh, Kob, off.shape[0], P)
+    keep = (dict(task), dict(ws), dict(tws), x, off, dict(hyper), plan_all, dplan_all, stream) + keep_more
     dev = x.device
     fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
 
     def step():
         rc = fn(*args, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc:
-            raise _lib.BcbfError("bcbf_unicycle_trigger_step failed (rc=%d): %s" % (rc, lib.bcbf_last_error().decode()))
+            raise _lib.BcbfError("%s failed (rc=%d): %s" % (entry, rc, lib.bcbf_last_error().decode()))
         return tws["dt_used"]
     step.keep = keep
     return step

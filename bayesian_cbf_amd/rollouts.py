@@ -179,7 +179,7 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
                             kernel_diag_A=(1e-2, 1e-2, 1e-2), L_mean=1.0, L_true=12.0, start=(-3.0, -1.0, -math.pi / 4),
                             goal=(0.0, 0.0, math.pi / 4), start_noise=0.05, max_risk=0.01, dtype=torch.float64, device="cuda",
                             seed=0, record=False, max_iters=30, use_graph=False, Nte=1e3, off=None, deltaL=1e-4, zeta=1e-2,
-                            L_alpha=1.0):
+                            L_alpha=1.0, plant="true", audit=False):
     """The closed loop that ACTS on the self-triggering time: Bt instances of the recipe of `monte_carlo_safety_rollouts` (same
     task, same start states for the same seed, true plant), but every instance re-solves when its model says the last control stops
     being safe, not every dt.  One EVENT is the control step with dt = 0 (solve only), the trigger step
@@ -194,12 +194,33 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     trigger_hyper = dict(ls, sf, A, B) (one model or one per instance).  Any data kernel but RBF is refused.  Nte / off: the test
     grid (`trigger_interval.default_test_grid`).  use_graph: capture one event and replay it (ignored with record).
     Returns dict(stats (`reduce_rollout_stats`; mean_cost is per event), x_final, t[Bt], events[Bt], events_per_second[Bt] =
-    events / t, done = share of instances with t == horizon, dt_used = dict(min, median, max) over all events taken, min_h,
+    events / t, done = share of instances with t == horizon, dt_used = dict(min, median, max) over all events taken,
+    share_at_tau_min = the share of those events held for exactly tau_min (clamped up to it: tau's promise is not in force), min_h,
     dist_to_goal, loop_seconds, task (the task tensors), and with record: rec = dict(x_before, u, status, tau, dt_used, t, x_after,
     active, and what the solve of the event read and formed: plan, dot_plan, Mk, Bk) of [max_events, Bt, ...] tensors, `active`
     telling which instances took that event (the rows of the others are stale)).
-    dt_used of every event is kept on the device ([max_events, Bt] in the working type) for the three figures."""
+    dt_used of every event is kept on the device ([max_events, Bt] in the working type) for the three figures.
+    plant: "true" (default) or "posterior": every event's plant is a draw from the model's OWN posterior at (x_e, u_e), xdot_s ~
+    N(fhat + ghat u + M_k ubar, (ubar' B_k ubar) A), held for the event's dt_b (`ops.unicycle_trigger_step_prepare` with `sampled`;
+    L_true is ignored): the distribution the chance constraint P(CBC_k >= 0) >= 1 - max_risk is stated under.  The standard
+    normals z_all[max_events, Bt, 3] are drawn once from the seeded generator, after the start noise; row e is gathered by the
+    device event counter, so the same seed gives the same run eager and under use_graph.  Each event's plant is ONE posterior draw
+    at (x_e, u_e) held for dt_b: exact per-event marginals, not one function drawn along the trajectory.  A held draw moves the
+    state by xdot_s dt_b, so the noise a trajectory accumulates depends on its event rate (n events of length h add a
+    displacement of standard deviation ~ sqrt(n) h; the same time in one event adds n h).  The result gains risk =
+    `distributed.reduce_risk_stats` over the SOLVED events of LIVE instances (an idle instance is not counted): how often an
+    obstacle row's condition was negative on the draw, to hold against max_risk.
+    audit: the control of every solved event is looked at again where it is released -- at the next event's state, on the rows that
+    event's solve wrote -- (`ops.unicycle_trigger_step_prepare` with `audit`): mean_k and margin_k = mean_k - rho std_k of every
+    obstacle row's condition under the HELD control.  tau promises margin_k >= 0 there; where the hold was clamped up to tau_min
+    the promise is not in force, and this is the measurement of what that costs.  The result gains audit = dict(events (audited),
+    neg_mean, neg_margin (per obstacle), rate_mean, rate_margin (over events x obstacles), min_mean, min_margin (per obstacle)).
+    With record, rec gains z, xdot_s, cbc_s (plant="posterior") and held (the flag BEFORE the event), held_mean, held_margin
+    (audit=True; rows are stale where held == 0 or the instance was idle).  The defaults are the loop as it was, bit for bit."""
     from . import trigger_interval as ti
+    if plant not in ("true", "posterior"):
+        raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    sampled = plant == "posterior"
     dev = torch.device(device)
     f = dict(dtype=dtype, device=dev)
     if gp is not None:
@@ -221,6 +242,7 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     task = unicycle_task_tensors(Bt, x0, xg, dtype, dev, max_risk=max_risk)
     planner = PiecewiseLinearPlanner(x0, xg, numSteps, dt, frac_time_to_reach_goal=0.95)
     x = (x0 + start_noise * torch.randn(Bt, 3, generator=gen, **f)).contiguous()
+    z_all = torch.randn(max_events, Bt, 3, generator=gen, **f) if sampled else None
     ws = ops.control_workspace(Bt, 2, dtype, dev)
     tws = ops.trigger_workspace(Bt, dtype, dev)
     if gp is None:
@@ -228,6 +250,9 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
         ws["Mk"].zero_()
         ws["Bk"].copy_(torch.eye(3, **f).expand(Bt, 3, 3))
         gp = dict(A=A)
+    aws = ops.trigger_audit_workspace(Bt, 2, dtype, dev) if (sampled or audit) else None
+    draw = aws["sampled"] if sampled else None
+    hold = aws["audit"] if audit else None
     off_np = ti.default_test_grid(3, Nte) if off is None else (off.detach().cpu().numpy() if torch.is_tensor(off) else off)
     r = ti._grid_norm(off_np)
     off = torch.as_tensor(off_np).to(**f).contiguous()
@@ -244,9 +269,14 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     t, events = tws["t"], tws["events"]
     solve = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=L_true, L_mean=L_mean, max_iters=max_iters)
     trigger = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, dt, horizon, tau_min, tau_max,
-                                                L_true=L_true, deltaL=deltaL, zeta=zeta, L_alpha=L_alpha)
+                                                L_true=L_true, deltaL=deltaL, zeta=zeta, L_alpha=L_alpha,
+                                                **(dict(gp_A=gp["A"], sampled=draw, audit=hold) if aws is not None else {}))
     gam, w_cost = task["gammas"], task["w"]
     state = [x, min_h, cost, fails, t, events, task["plan"], task["dot_plan"], dt_hist, act_hist, ectr]
+    if sampled:
+        state += [draw["viol"], draw["solved"], draw["min_cbc"]]
+    if audit:
+        state += [hold[k] for k in ("u_held", "held", "audit_n", "audit_neg", "audit_min")]
     rec = None
     if record:
         rec = dict(x_before=torch.empty(max_events, Bt, 3, **f), u=torch.empty(max_events, Bt, 2, **f),
@@ -255,10 +285,17 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
                    x_after=torch.empty(max_events, Bt, 3, **f), active=act_hist, plan=torch.empty(max_events, Bt, 3, **f),
                    dot_plan=torch.empty(max_events, Bt, 3, **f), Mk=torch.empty(max_events, Bt, 3, 3, **f),
                    Bk=torch.empty(max_events, Bt, 3, 3, **f))
+        if sampled:
+            rec.update(z=z_all, xdot_s=torch.empty(max_events, Bt, 3, **f), cbc_s=torch.empty(max_events, Bt, 3, **f))
+        if audit:
+            rec.update(held=torch.empty(max_events, Bt, dtype=torch.int32, device=dev), held_mean=torch.empty(max_events, Bt, 2, **f),
+                       held_margin=torch.empty(max_events, Bt, 2, **f))
 
     def one_event():
         torch.lt(t, horizon, out=active)          # who takes this event (the trigger step leaves the others alone)
         solve()                                   # rows -> terms -> SOCP at the current state, no plant
+        if sampled:                               # this event's draws, by the device event counter
+            draw["z"].copy_(z_all.index_select(0, ectr)[0])
         trigger()                                 # tau, the plant over the time the control is held, clock, planner rows
         # the bookkeeping of `monte_carlo_safety_rollouts`, per event; an idle instance's cost and failure count are put back
         # (its min_h cannot change: its state does not)
@@ -294,6 +331,8 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
             continue
         if record:
             rec["x_before"][e], rec["plan"][e], rec["dot_plan"][e] = x, task["plan"], task["dot_plan"]
+            if audit:
+                rec["held"][e] = hold["held"]
         one_event()
         if record:
             rec["u"][e], rec["Mk"][e], rec["Bk"][e] = ws["y"][:, :2], ws["Mk"], ws["Bk"]
@@ -301,6 +340,10 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
             rec["tau"][e] = tws["tau"]
             rec["t"][e] = t
             rec["x_after"][e] = x
+            if sampled:
+                rec["xdot_s"][e], rec["cbc_s"][e] = draw["xdot_s"], draw["cbc_s"]
+            if audit:
+                rec["held_mean"][e], rec["held_margin"][e] = hold["held_mean"], hold["held_margin"]
     torch.cuda.synchronize(dev)
     t_loop = time.perf_counter() - t_loop
     collided = ~(min_h >= 0)
@@ -308,8 +351,20 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     stats = reduce_rollout_stats(collided.sum(), min_h.min(), per_event_cost.sum(), (fails > 0).sum(), Bt)
     taken = dt_hist[act_hist]
     dt_used = dict(min=float(taken.min()), median=float(taken.median()), max=float(taken.max())) if taken.numel() else None
+    at_min = float((taken == torch.tensor(tau_min, **f)).double().mean()) if taken.numel() else None
     out = dict(stats=stats, x_final=x, t=t, events=events, events_per_second=events.double() / t, done=float((t >= horizon).double().mean()),
-               dt_used=dt_used, min_h=min_h, dist_to_goal=(x[:, :2] - xg[:2]).norm(dim=1), loop_seconds=t_loop, task=task, rec=rec)
+               dt_used=dt_used, min_h=min_h, dist_to_goal=(x[:, :2] - xg[:2]).norm(dim=1), loop_seconds=t_loop, task=task, rec=rec,
+               share_at_tau_min=at_min)
+    if sampled:
+        out["risk"] = reduce_risk_stats(draw["solved"].sum(), draw["viol"].sum(0), draw["min_cbc"].min(0).values, max_risk)
+    if audit:
+        n = int(hold["audit_n"].sum())
+        neg = hold["audit_neg"].sum(0).tolist()                        # [Kob][mean, margin]
+        mins = hold["audit_min"].min(0).values.double().tolist()
+        rows = max(len(neg), 1)
+        out["audit"] = dict(events=n, neg_mean=[int(v[0]) for v in neg], neg_margin=[int(v[1]) for v in neg],
+                            rate_mean=sum(v[0] for v in neg) / max(n * rows, 1), rate_margin=sum(v[1] for v in neg) / max(n * rows, 1),
+                            min_mean=[float(v[0]) for v in mins], min_margin=[float(v[1]) for v in mins])
     return out
 
 

@@ -6,6 +6,7 @@ over the GPUs of one node (contiguous shard per rank, no collective inside the l
     python examples_mc_rollouts.py --gpus 8 --trajectories 32768 --steps 200 --graph        # starts its 8 ranks itself
     python examples_mc_rollouts.py --plant posterior --max-risk 0.05 --graph     # plants drawn from the model's posterior: `risk`
     python examples_mc_rollouts.py --trigger self --tau-min 1e-3 --tau-max 0.05 --compare-periodic --graph   # the loop that acts on tau
+    python examples_mc_rollouts.py --trigger self --plant posterior --audit --max-risk 0.05 --graph   # ... on drawn plants: `risk`, `audit`
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         examples_mc_rollouts.py --gpus 8 --trajectories 32768 --steps 200
 
@@ -28,24 +29,31 @@ if ROOT not in sys.path:
 def self_triggered(args, ctx, gp, dtype, n_loc):
     """--trigger self: `rollouts.self_triggered_rollouts` over the horizon the periodic loop covers (steps x its dt = 0.05)."""
     from bayesian_cbf_amd.rollouts import monte_carlo_safety_rollouts, self_triggered_rollouts
-    if ctx.world != 1 or args.plant != "true":
-        sys.exit("--trigger self runs on one GPU with the true plant")
+    if ctx.world != 1:
+        sys.exit("--trigger self runs on one GPU")
     dt = 0.05
     hyper = None
     if gp is None:      # the fixed-kernel model has no data kernel: unit lengthscales and scale, its A and B
         hyper = dict(ls=[1.0, 1.0, 1.0], sf=1.0, A=torch.diag(torch.tensor([1e-2, 1e-2, 1e-2], dtype=torch.float64)), B=torch.eye(3))
     out = self_triggered_rollouts(n_loc, horizon=args.steps * dt, dt=dt, gp=gp, trigger_hyper=hyper, tau_min=args.tau_min,
                                   tau_max=args.tau_max, max_risk=args.max_risk, seed=ctx.rank, dtype=dtype, device=ctx.device,
-                                  use_graph=args.graph, zeta=args.zeta)
+                                  use_graph=args.graph, zeta=args.zeta, plant=args.plant, audit=args.audit)
     ev = out["events"].double()
     line = dict(config="c4 self-triggered: the loop that acts on tau", trajectories=n_loc, horizon=args.steps * dt, tau_min=args.tau_min,
                 tau_max=args.tau_max, zeta=args.zeta, done=out["done"], events_mean=float(ev.mean()), events_max=int(ev.max()),
                 events_per_second_mean=float(out["events_per_second"].mean()), periodic_events=args.steps, dt_used=out["dt_used"],
-                loop_seconds=out["loop_seconds"], **out["stats"])
+                loop_seconds=out["loop_seconds"], plant=args.plant, **out["stats"])
+    line["share_of_events_at_tau_min"] = out["share_at_tau_min"]
+    if args.plant == "posterior":
+        line["risk"] = out["risk"]
+    if args.audit:
+        line["audit"] = out["audit"]
     if args.compare_periodic:
         per = monte_carlo_safety_rollouts(n_loc, numSteps=args.steps, dt=dt, gp=gp, max_risk=args.max_risk, seed=ctx.rank, dtype=dtype,
-                                          device=ctx.device, use_graph=args.graph)
+                                          device=ctx.device, use_graph=args.graph, plant=args.plant)
         line["periodic"] = dict(per["stats"], loop_seconds=per["loop_seconds"], events_per_second=1.0 / dt)
+        if args.plant == "posterior":
+            line["periodic"]["risk"] = per["risk"]
     if ctx.rank == 0:
         print(json.dumps(line))
 
@@ -62,7 +70,10 @@ def main():
                          "empirical rate at which an obstacle condition is negative on the draw, to hold against --max-risk")
     ap.add_argument("--trigger", choices=["periodic", "self"], default="periodic",
                     help="self: every trajectory re-solves when its self-triggering time tau runs out (clamped to [--tau-min, --tau-max]) "
-                         "instead of every planner step; one GPU, true plant; prints its own JSON line")
+                         "instead of every planner step; one GPU; prints its own JSON line (with --plant posterior: `risk`)")
+    ap.add_argument("--audit", action="store_true",
+                    help="--trigger self: look at every held control again where it is released (mean and margin of each obstacle "
+                         "condition under it at the next event's state); the JSON line gains `audit`")
     ap.add_argument("--tau-min", type=float, default=1e-3)
     ap.add_argument("--tau-max", type=float, default=0.05)
     ap.add_argument("--zeta", type=float, default=1e-2, help="--trigger self: the safety margin zeta of the trigger time")

@@ -204,6 +204,64 @@ int bcbf_unicycle_trigger_step_f64(double* x, const double* y, const int* status
                                    double* tau, double* dt_used, double* Lfh, double* Lkd, double* Lh, double* xvel, double* uBu, int Bt,
                                    int Bh, int Kob, int Nte, int P, void* stream);
 
+/* bcbf_unicycle_trigger_step with the plant drawn from the model's own posterior over the variable hold, and an audit of the
+ * held control at the moment it is released: the same launch (one workgroup per instance, same pair loop and closed forms), the
+ * new work done by one thread in fp64 from the values as the working type stores them, every output rounded once, no atomics.
+ * It follows the FUSED solve (bcbf_unicycle_control_step[_kind] with dt = 0), whose rows it reads: Bk[Bt,3,3], A[Bt,3,3],
+ * grad[Bt,1+Kob,3], cst[Bt,1+Kob], the task's sign[1+Kob] and rho[Bt] (all required), so Kob + 1 <= BCBF_MAX_QUAD_CONSTRAINTS.
+ * Everything bcbf_unicycle_trigger_step writes that does not depend on the plant (tau, Lfh, Lkd, Lh, xvel, uBu, dt_used, t,
+ * events, plan, dot_plan) is bit-identical to that entry's; with z == NULL so is x.  A finished instance (t[b] >= t_end) leaves
+ * before anything of it is read or written, the new buffers included.
+ *  Group P, the posterior plant -- present when z[Bt,3] (the caller's standard normals) is non-NULL; xdot_s[Bt,3] and
+ *  cbc_s[Bt,1+Kob] optional; viol[Bt,Kob], solved[Bt] (int32), min_cbc[Bt,Kob] optional, all three or none:
+ *   a solved instance steps by the draw instead of the true drive (L_true is ignored):
+ *     xdot_s = fhat + ghat u + M_k ubar + sqrt(max(ubar' B_k ubar, 0)) L_A z,  A = L_A L_A' (a pivot <= 0 zeroes its column),
+ *     x[b] = (T)(x[b] + xdot_s dt_b)  with dt_b the hold under the clamp rules above, as the working type holds it,
+ *     cbc_s[b,k] = sign_k (grad_k . xdot_s + cst_k) for every row, the CLC row included
+ *   -- the arithmetic of bcbf_unicycle_control_step_sampled, which takes no plant step when called with dt = 0;
+ *   an unsolved instance keeps its state, gets xdot_s = 0, cbc_s = 0 and lets min(tau_max, t_end - t[b]) pass;
+ *   the counters of a solved instance: solved[b] += 1, viol[b,k-1] += (cbc_s[b,k] < 0 or non-finite) and min_cbc the running
+ *   minimum (a non-finite value entering as -inf), k = 1..Kob, on cbc_s as stored: bcbf_rollout_risk's semantics, done here
+ *   because that entry cannot tell an idle instance from a live one.
+ *  Group H, the held-control audit -- present when u_held is non-NULL (then all seven buffers are), independent of group P:
+ *  u_held[Bt,2] and held[Bt] (int32) in/out; held_mean[Bt,Kob], held_margin[Bt,Kob] out; audit_n[Bt], audit_neg[Bt,Kob,2]
+ *  (int32) and audit_min[Bt,Kob,2] in/out counters:
+ *   where held[b] != 0, before anything else of the event and whatever its status, on the rows the solve of THIS event wrote at
+ *   the current state, with ubar_h = (1, u_held[b]) and for every obstacle row k = 1..Kob:
+ *     mean_k   = sign_k (grad_k . (fhat + ghat u_held + M_k ubar_h) + cst_k)
+ *     std_k    = sqrt(max((ubar_h' B_k ubar_h) (grad_k' A grad_k), 0))
+ *     margin_k = mean_k - rho[b] std_k                         (the two sides of the cone the control was solved under)
+ *   held_mean[b,k-1] and held_margin[b,k-1] are written, audit_n[b] += 1, audit_neg[b,k-1,0] += !(mean_k >= 0),
+ *   audit_neg[b,k-1,1] += !(margin_k >= 0) (NaN counts as negative) and audit_min[b,k-1,:] takes the running minima (NaN
+ *   entering as -inf), all on the values as stored;  where held[b] == 0 -- an instance's first event, and the event after an
+ *   unsolved one -- nothing is audited and the output rows are not written;
+ *   at the end of the event u_held[b] = u of this event and held[b] = (status[b] == BCBF_SOCP_OPTIMAL).
+ * Limits: those of bcbf_unicycle_trigger_step, and Kob <= BCBF_MAX_QUAD_CONSTRAINTS - 1, the six rows non-NULL, no optional
+ * buffer of group P without z, each group's counters complete; otherwise BCBF_EINVAL before any HIP call, reason in
+ * bcbf_last_error.  No allocation, no host synchronisation: capturable. */
+int bcbf_unicycle_trigger_step_audit_f32(float* x, const float* y, const int* status, const float* fhat, const float* ghat,
+                                         const float* Mk, const float* centers, const float* tw, const float* off, double r,
+                                         const float* ls, const float* sf, const float* Adiag, const float* Bhyp, double deltaL,
+                                         double zeta, double L_alpha, double tau_min, double tau_max, double t_end, float L_true,
+                                         const float* plan_all, const float* dplan_all, double dt_plan, double* t, int* events,
+                                         float* plan, float* dot_plan, float* tau, float* dt_used, float* Lfh, float* Lkd, float* Lh,
+                                         float* xvel, float* uBu, const float* Bk, const float* A, const float* grad,
+                                         const float* cst, const float* sign, const float* rho, const float* z, float* xdot_s,
+                                         float* cbc_s, int* viol, int* solved, float* min_cbc, float* u_held, int* held,
+                                         float* held_mean, float* held_margin, int* audit_n, int* audit_neg, float* audit_min, int Bt,
+                                         int Bh, int Kob, int Nte, int P, void* stream);
+int bcbf_unicycle_trigger_step_audit_f64(double* x, const double* y, const int* status, const double* fhat, const double* ghat,
+                                         const double* Mk, const double* centers, const double* tw, const double* off, double r,
+                                         const double* ls, const double* sf, const double* Adiag, const double* Bhyp, double deltaL,
+                                         double zeta, double L_alpha, double tau_min, double tau_max, double t_end, double L_true,
+                                         const double* plan_all, const double* dplan_all, double dt_plan, double* t, int* events,
+                                         double* plan, double* dot_plan, double* tau, double* dt_used, double* Lfh, double* Lkd,
+                                         double* Lh, double* xvel, double* uBu, const double* Bk, const double* A, const double* grad,
+                                         const double* cst, const double* sign, const double* rho, const double* z, double* xdot_s,
+                                         double* cbc_s, int* viol, int* solved, double* min_cbc, double* u_held, int* held,
+                                         double* held_mean, double* held_margin, int* audit_n, int* audit_neg, double* audit_min,
+                                         int Bt, int Bh, int Kob, int Nte, int P, void* stream);
+
 /* K2 on a caller-supplied dense SPD matrix (lower triangle of Kb[Bt,N,N] is read): same outputs.
  * Replaces torch.linalg.cholesky (control_affine_model.py:911). */
 int bcbf_potrf_f32(const float* Kb, float* Lop, float* Ldense, int* info, int Bt, int N, void* stream);

@@ -11,7 +11,13 @@ anything is timed.  The sequence cannot hold every instance's control for its OW
 batch): it is timed with one dt, which flatters it.  tau_max = 1e-6 keeps the state where it is over the timed repetitions, so
 every repetition of either form sees the same inputs to six digits.  HIP events around back-to-back calls after a warm-up that
 raises the clocks (tools/_timing.py); the fused step, the sequence and the pair kernel alone are timed three times in alternation and
-the medians reported (all nine figures are kept)."""
+the medians reported (all nine figures are kept).
+
+    python tools/bench_self_triggered.py --plant posterior --audit [--out profiles/self_triggered_posterior.json]
+
+times, in the same alternating scheme, the plain trigger step against bcbf_unicycle_trigger_step_audit on the same inputs (the plant
+drawn from the posterior with its risk counters, the audit of the held control, or both, as the flags say) and nothing else: the
+medians of three, all six figures, and the plain step's own run-to-run spread (max - min over its three) beside the difference."""
 import argparse
 import json
 import math
@@ -32,8 +38,14 @@ def main():
     ap.add_argument("--B", type=int, default=4096)
     ap.add_argument("--Nte", type=float, default=1e3, help="rounded down to a cube, as the reference does (1e3 -> 729)")
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "self_triggered.json"))
+    ap.add_argument("--plant", choices=["true", "posterior"], default="true",
+                    help="posterior: time the trigger step on the posterior-drawn plant against the plain one (with --audit: both groups)")
+    ap.add_argument("--audit", action="store_true", help="time the trigger step with the held-control audit against the plain one")
+    ap.add_argument("--out", default=None, help="default profiles/self_triggered.json, or self_triggered_posterior.json with --plant posterior / --audit")
     args = ap.parse_args()
+    compare_new = args.plant == "posterior" or args.audit
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "self_triggered_posterior.json" if compare_new else "self_triggered.json")
     if not torch.cuda.is_available():
         sys.exit("bench_self_triggered needs the GPU: nothing is measured without it")
     from bayesian_cbf_amd import ops
@@ -43,8 +55,9 @@ def main():
     grid = ti.default_test_grid(3, args.Nte)
     Nte, Bt = grid.shape[0], args.B
     r = ti._grid_norm(grid)
-    res = dict(B=Bt, Nte=Nte, device=torch.cuda.get_device_name(0), reps=args.reps,
-               pair_part_alone_ms_f32_recorded=0.372)            # profiles/trigger_interval.json, the only figure measured before
+    res = dict(B=Bt, Nte=Nte, device=torch.cuda.get_device_name(0), reps=args.reps)
+    if not compare_new:
+        res["pair_part_alone_ms_f32_recorded"] = 0.372            # profiles/trigger_interval.json, the only figure measured before
     L_true, L_mean, dt_ref = 12.0, 1.0, 0.01
     for dtype, name in ((torch.float32, "f32"), (torch.float64, "f64")):
         f = dict(dtype=dtype, device="cuda")
@@ -71,6 +84,25 @@ def main():
         plan_all, dplan_all = task["plan"][:1].expand(P, 3).contiguous(), task["dot_plan"][:1].expand(P, 3).contiguous()
         fused = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, 0.05, 1e9, 1e-9, 1e-6,
                                                   L_true=L_true)
+        if compare_new:
+            aws = ops.trigger_audit_workspace(Bt, 2, dtype, "cuda")
+            aws["sampled"]["z"].copy_(torch.randn(Bt, 3, generator=gen, **f))
+            new = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, 0.05, 1e9, 1e-9, 1e-6, L_true=L_true,
+                                                    gp_A=gp["A"], sampled=aws["sampled"] if args.plant == "posterior" else None,
+                                                    audit=aws["audit"] if args.audit else None)
+            fused()
+            new()                                   # (from here on every solved instance has a held control to audit)
+            torch.cuda.synchronize()
+            runs = [[timeit(fn, reps=args.reps) for fn in (fused, new)] for _ in range(3)]      # alternating; the medians count
+            plain_ms, new_ms = (sorted(col)[1] for col in zip(*runs))
+            plain_runs = [q[0] for q in runs]
+            res[name] = dict(plain_trigger_step_ms=plain_ms, audit_trigger_step_ms=new_ms, plant=args.plant, audit=bool(args.audit),
+                             added_ms=new_ms - plain_ms, added_over_plain=new_ms / plain_ms - 1.0,
+                             plain_spread_ms=max(plain_runs) - min(plain_runs), solved=int((ws["status"] == 0).sum()),
+                             audited_events=int(aws["audit"]["audit_n"].sum()), counted_events=int(aws["sampled"]["solved"].sum()),
+                             alternating_runs_ms=dict(plain=plain_runs, audit_entry=[q[1] for q in runs]))
+            print(json.dumps({name: res[name]}))
+            continue
         cbfs = [ObstacleCBF(task["centers"][:, k], task["radii"][:, k], (0.7, 0.3)) for k in range(2)]
         x_seq = x.clone()
         u = ws["y"][:, :2].contiguous()
