@@ -63,6 +63,8 @@ _TSIGS = {
     "bcbf_unicycle_trigger_step": [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11 + [c_int] * 5 + [P],
     "bcbf_unicycle_trigger_step_audit": [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11 + [P] * 19
                                         + [c_int] * 5 + [P],
+    "bcbf_unicycle_trigger_step_observe": [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11 + [P] * 19
+                                          + [c_float, P, P, P, c_int, c_int, c_int, P, c_int] + [c_int] * 5 + [P],
     "bcbf_potrs": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_chol_append": [P, P, P, P, P, c_int, c_int, P],
     "bcbf_gp_append": [P] * 17 + [c_int, c_int, c_int, c_int, P],

@@ -28,8 +28,17 @@
 //   the audit of the held control (u_held given): the two sides of every obstacle row's cone, mean >= rho std, evaluated with
 //     the control of the instance's PREVIOUS event on the rows the solve of this event wrote at the state where that control is
 //     released -- what tau promised, measured one launch later.
+//
+// bcbf_unicycle_trigger_step_observe is that launch with a third optional piece of work for thread 0, after the plant step (the
+// third instantiation of trigger_step_body; the code of the first two does not change with it): the event as the learner's
+// observation row -- unicycle_observe (unicycle_task.h), the function the periodic solve / plant launch calls, on the states as
+// stored and with the event's own hold dt_b in place of the batch's dt -- written to the stream row the instance's OWN event
+// count names, so one captured graph serves every event, and the shift-invariant query of the next solve.  Plain vector stores
+// from one lane, no atomics.
 #include "trigger_pairs.h"
+#include "unicycle_task.h"
 #include <stdio.h>
+#include <type_traits>
 
 namespace bcbf {
 
@@ -55,6 +64,14 @@ struct TriggerAuditArgs {
     T* u_held; int* held; T* held_mean; T* held_margin; int* audit_n; int* audit_neg; T* audit_min;
 };
 struct TriggerNoAudit {};
+
+// what bcbf_unicycle_trigger_step_observe adds to those: the observation stream (obs_x == nullptr: no rows) and the next query
+// (xq_next == nullptr: none)
+template <typename T>
+struct TriggerObserveArgs {
+    T L_mean; T* obs_x; T* obs_uh; T* obs_y; int obs_ld, obs_row0, obs_every; T* xq_next; int shift_invariant;
+};
+struct TriggerNoObserve {};
 
 // sum or maximum of v over the workgroup, through red[slot] (every slot is used once per launch: no barrier after the read)
 __device__ inline double block_reduce(double v, double (*red)[TI_WAVES], int slot, bool is_max) {
@@ -183,9 +200,36 @@ __device__ inline void posterior_plant_step(const TriggerStepArgs<T>& a, const T
     }
 }
 
-// The event of one instance by its workgroup.  AUDIT = false, Q = TriggerNoAudit: bcbf_unicycle_trigger_step.
-template <typename T, bool AUDIT, typename Q>
-__device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, const Q& au) {
+// The observation of the event (one thread, after the plant step): row obs_row0 + e / obs_every of instance b's stream when its
+// event count e (before the increment) is a multiple of obs_every and the row exists, and the next query at every event
+template <typename T>
+__device__ inline void observe_event(const TriggerStepArgs<T>& a, const TriggerObserveArgs<T>& o, int b, const T (&xb)[3], T u0, T u1,
+                                     bool solved, T dt) {
+    UnicycleTask<T> task = {};
+    task.L_mean = o.L_mean;
+    task.dt = dt;
+    task.shift_invariant = o.shift_invariant;
+    task.advance_plan = 0;
+    task.xq_next = o.xq_next;
+    const int e = a.events[b];
+    if (o.obs_x != nullptr && e >= 0 && e % o.obs_every == 0) {
+        const long long k = (long long)o.obs_row0 + e / o.obs_every;
+        if (k < (long long)o.obs_ld) {                 // (a row past the stream is skipped: nothing is written outside the buffer)
+            task.obs_x = o.obs_x + (size_t)k * 3;      // unicycle_observe writes row b * obs_ld of what it is handed
+            task.obs_uh = o.obs_uh + (size_t)k * 3;
+            task.obs_y = o.obs_y + (size_t)k * 3;
+            task.obs_ld = o.obs_ld;
+        }
+    }
+    // the state as the plant step stored it (the true drive's or the draw's); an unsolved instance kept its own and applied u = 0
+    const T n0 = a.x[(size_t)b * 3], n1 = a.x[(size_t)b * 3 + 1], n2 = a.x[(size_t)b * 3 + 2];
+    unicycle_observe<T>(task, b, xb[0], xb[1], xb[2], n0, n1, n2, solved ? u0 : T(0), solved ? u1 : T(0));
+}
+
+// The event of one instance by its workgroup.  AUDIT = false, Q = TriggerNoAudit: bcbf_unicycle_trigger_step; O = TriggerNoObserve:
+// that entry and bcbf_unicycle_trigger_step_audit.
+template <typename T, bool AUDIT, typename Q, typename O = TriggerNoObserve>
+__device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, const Q& au, const O& ob = O{}) {
     constexpr int NS = 3, ST = ti_stride(NS);
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_raw[];
     __shared__ T ts_red[TI_WAVES][NS];
@@ -288,6 +332,7 @@ __device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, c
         a.x[(size_t)b * 3 + 2] = th + u1 / a.L_true * dtT;
     }
     if (a.dt_used) a.dt_used[b] = dtT;
+    if constexpr (!std::is_same<O, TriggerNoObserve>::value) observe_event<T>(a, ob, b, xb, u0, u1, solved, dtT);   // ... what the learner sees of it
     // ... the clock (the step taken, as the plant saw it; the last one lands on t_end itself), the count and the planner's rows
     const double t1 = last ? a.t_end : t0 + (double)dtT;
     a.t[b] = t1;
@@ -309,6 +354,12 @@ __global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const
 template <typename T>
 __global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_audit_kernel(const TriggerStepArgs<T> a, const TriggerAuditArgs<T> q) {
     trigger_step_body<T, true>(a, q);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_observe_kernel(const TriggerStepArgs<T> a, const TriggerAuditArgs<T> q,
+                                                                                   const TriggerObserveArgs<T> o) {
+    trigger_step_body<T, true>(a, q, o);
 }
 
 template <typename T>
@@ -379,6 +430,38 @@ static int launch_trigger_step_audit(const char* entry, TriggerStepArgs<T> a, co
     return check_launch(entry);
 }
 
+template <typename T>
+static int trigger_observe_args_ok(const char* entry, const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, const TriggerObserveArgs<T>& o,
+                                   int flags, int Bt, int Bh) {
+    if (!trigger_audit_args_ok<T>(entry, a, q, Bt, Bh)) return 0;
+    static thread_local char msg[280];
+    const int rows = (o.obs_x != nullptr) + (o.obs_uh != nullptr) + (o.obs_y != nullptr);
+    const char* why = nullptr;
+    if (rows != 0 && rows != 3) why = "the observation rows (obs_x, obs_uh, obs_y) are given together or not at all";
+    else if (rows && o.obs_ld < 1) why = "obs_ld < 1";
+    else if (rows && o.obs_row0 < 0) why = "obs_row0 < 0";
+    else if (rows && o.obs_every < 1) why = "obs_every < 1";
+    else if (rows && (o.L_mean != o.L_mean || o.L_mean == T(0))) why = "L_mean must be a number other than 0 (the rows subtract g(theta; L_mean) u)";
+    else if (flags & ~1) why = "flags: only bit 0 (shift-invariant inputs) is defined";
+    if (!why) return 1;
+    snprintf(msg, sizeof(msg), "%s: %s (Bt=%d rows=%d/3 obs_ld=%d obs_row0=%d obs_every=%d L_mean=%g flags=%d)", entry, why, Bt, rows,
+             o.obs_ld, o.obs_row0, o.obs_every, (double)o.L_mean, flags);
+    set_error_message(msg);
+    return 0;
+}
+
+template <typename T>
+static int launch_trigger_step_observe(const char* entry, TriggerStepArgs<T> a, const TriggerAuditArgs<T>& q, const TriggerObserveArgs<T>& o,
+                                       int flags, int Bt, int Bh, void* stream) {
+    if (!trigger_observe_args_ok<T>(entry, a, q, o, flags, Bt, Bh)) return BCBF_EINVAL;
+    a.per_instance_hyper = Bh == Bt && Bt > 1 ? 1 : 0;
+    const size_t lds = (size_t)a.Nte * ti_stride(3) * sizeof(T);
+    if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_observe_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((unicycle_trigger_step_observe_kernel<T>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a, q, o);
+    return check_launch(entry);
+}
+
 }  // namespace bcbf
 
 #define BCBF_TRIGGER_STEP(T, SUF)                                                                                                 \
@@ -415,3 +498,24 @@ BCBF_TRIGGER_STEP(double, f64)
 BCBF_TRIGGER_STEP_AUDIT(float, f32)
 BCBF_TRIGGER_STEP_AUDIT(double, f64)
 #undef BCBF_TRIGGER_STEP_AUDIT
+
+#define BCBF_TRIGGER_STEP_OBSERVE(T, SUF)                                                                                         \
+    extern "C" int bcbf_unicycle_trigger_step_observe_##SUF(                                                                      \
+        T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off, \
+        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, \
+        double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, int* events, T* plan, \
+        T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu, const T* Bk, const T* A, const T* grad, const T* cst, \
+        const T* sign, const T* rho, const T* z, T* xdot_s, T* cbc_s, int* viol, int* solved, T* min_cbc, T* u_held, int* held,   \
+        T* held_mean, T* held_margin, int* audit_n, int* audit_neg, T* audit_min, float L_mean, T* obs_x, T* obs_uh, T* obs_y,     \
+        int obs_ld, int obs_row0, int obs_every, T* xq_next, int flags, int Bt, int Bh, int Kob, int Nte, int P, void* stream) {   \
+        bcbf::TriggerStepArgs<T> a = {x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, \
+                                      tau_min, tau_max, t_end, L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, \
+                                      dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P};                                          \
+        const bcbf::TriggerAuditArgs<T> q = {Bk, A, grad, cst, sign, rho, z, xdot_s, cbc_s, viol, solved, min_cbc, u_held, held,  \
+                                             held_mean, held_margin, audit_n, audit_neg, audit_min};                              \
+        const bcbf::TriggerObserveArgs<T> o = {(T)L_mean, obs_x, obs_uh, obs_y, obs_ld, obs_row0, obs_every, xq_next, flags & 1}; \
+        return bcbf::launch_trigger_step_observe<T>("bcbf_unicycle_trigger_step_observe_" #SUF, a, q, o, flags, Bt, Bh, stream);   \
+    }
+BCBF_TRIGGER_STEP_OBSERVE(float, f32)
+BCBF_TRIGGER_STEP_OBSERVE(double, f64)
+#undef BCBF_TRIGGER_STEP_OBSERVE

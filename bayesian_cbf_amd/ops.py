@@ -1432,6 +1432,50 @@ def trigger_audit_workspace(Bt, Kob, dtype, device):
     return dict(sampled=sampled, audit=audit)
 
 
+def trigger_observe_workspace(Bt, rows, dtype, device):
+    """The observation stream of `unicycle_trigger_step_prepare(observe=...)` (bcbf_unicycle_trigger_step_observe), as the dict that
+    call takes: obs = (X[Bt,rows,3], UH[Bt,rows,3], Y[Bt,rows,3]), ld = rows, row0 = 0, every = 1, xq_next[Bt,3] (zero),
+    shift_invariant = True, L_mean = 1.0 -- change row0 / every / L_mean in the dict before binding.  Every row starts as the plant
+    AT REST, X = 0, UH = (1, 0, 0), Y = 0: a true, uninformative observation (u = 0 moves nothing), so a row that is never written --
+    the instance finished, or its row index is past the stream -- is still a valid training row (U = 0 for the oracle)."""
+    f = dict(dtype=dtype, device=device)
+    UH = torch.zeros(Bt, rows, 3, **f)
+    UH[:, :, 0] = 1
+    return dict(obs=(torch.zeros(Bt, rows, 3, **f), UH, torch.zeros(Bt, rows, 3, **f)), ld=int(rows), row0=0, every=1,
+                xq_next=torch.zeros(Bt, 3, **f), shift_invariant=True, L_mean=1.0)
+
+
+_TRIGGER_OBSERVE_KEYS = ("obs", "ld", "row0", "every", "xq_next", "shift_invariant", "L_mean")
+
+
+def _trigger_observe_check(x, observe):
+    """Shape and dtype checks (ValueError) of group O; returns ([obs_x, obs_uh, obs_y, xq_next] (None where absent), the entry's
+    scalar arguments (L_mean, ld, row0, every, flags))."""
+    Bt = x.shape[0]
+    unknown = set(observe) - set(_TRIGGER_OBSERVE_KEYS)
+    if unknown:
+        raise ValueError("trigger step: observe has no key %s" % sorted(unknown))
+    obs, xq_next = observe.get("obs"), observe.get("xq_next")
+    ld, row0, every = (int(observe.get(k, d)) for k, d in (("ld", 1), ("row0", 0), ("every", 1)))
+    L_mean = float(observe.get("L_mean", 1.0))
+    if obs is not None:
+        if len(obs) != 3 or any(v is None for v in obs):
+            raise ValueError("trigger step: observe['obs'] is the three stream buffers (obs_x, obs_uh, obs_y), or None")
+        if ld < 1 or row0 < 0 or every < 1:
+            raise ValueError("trigger step: observe needs ld >= 1, row0 >= 0, every >= 1 (got %d, %d, %d)" % (ld, row0, every))
+        if not (L_mean != 0.0 and L_mean == L_mean):
+            raise ValueError("trigger step: observe['L_mean'] must be a number other than 0")
+        for name, v in zip(("obs_x", "obs_uh", "obs_y"), obs):
+            if v.dtype != x.dtype or not v.is_contiguous() or tuple(v.shape) != (Bt, ld, 3):
+                raise ValueError("trigger step: observe['obs'] %s (%s %s) must be a contiguous %s tensor of shape %s"
+                                 % (name, v.dtype, tuple(v.shape), x.dtype, (Bt, ld, 3)))
+    if xq_next is not None and (xq_next.dtype != x.dtype or not xq_next.is_contiguous() or tuple(xq_next.shape) != (Bt, 3)):
+        raise ValueError("trigger step: observe['xq_next'] (%s %s) must be a contiguous %s tensor of shape %s"
+                         % (xq_next.dtype, tuple(xq_next.shape), x.dtype, (Bt, 3)))
+    tensors = (list(obs) if obs is not None else [None] * 3) + [xq_next]
+    return tensors, (L_mean, ld, row0, every, 1 if observe.get("shift_invariant", True) else 0)
+
+
 _TRIGGER_SAMPLED_KEYS = ("z", "xdot_s", "cbc_s", "viol", "solved", "min_cbc")
 _TRIGGER_AUDIT_KEYS = ("u_held", "held", "held_mean", "held_margin", "audit_n", "audit_neg", "audit_min")
 
@@ -1483,7 +1527,8 @@ def _trigger_audit_check(task, ws, x, gp_A, sampled, audit):
 
 
 def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, dt_plan, t_end, tau_min, tau_max,
-                                  L_true=1.0, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, stream=None, gp_A=None, sampled=None, audit=None):
+                                  L_true=1.0, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, stream=None, gp_A=None, sampled=None, audit=None,
+                                  observe=None):
     """Bind the buffers of one EVENT of the self-triggered loop once and return `step()` (bcbf_unicycle_trigger_step, one launch):
     run it after the `step()` of `unicycle_control_step_prepare(..., dt=0)` on the same task / ws / x.  It computes the trigger
     time tau of the control in ws['y'] (uBu, xvel, Lh, Lkd, Lfh, tau as `trigger_interval.trigger_interval_batch` does, on the test
@@ -1502,9 +1547,18 @@ def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dpl
     audit = dict(u_held, held, held_mean, held_margin, audit_n, audit_neg, audit_min), all seven: where the instance's previous
     event was solved, the mean and the margin mean - rho std of every obstacle row's condition under the control of THAT event,
     on this event's rows (the state where the control is released), with counts of negative values and running minima.
-    With neither it is the plain entry, unchanged."""
+    observe = dict(obs=(obs_x, obs_uh, obs_y) | None, ld, row0, every, xq_next | None, shift_invariant, L_mean) (from
+    `trigger_observe_workspace`; needs gp_A too, composes with sampled / audit) binds bcbf_unicycle_trigger_step_observe: the loop
+    LEARNS FROM ITSELF.  After the plant step the event is written as an observation row -- input = the state before the step,
+    (0, 0, theta) when shift_invariant; (1, u); target = (x_new - x_old) / dt_b - g(theta; L_mean) u with the event's own hold dt_b;
+    an unsolved instance writes the plant at rest -- into row row0 + e // every of the instance's stream obs_*[Bt, ld, 3], e its
+    event count before the event, when e % every == 0 and the row exists (a row past ld is skipped), and the regressor's input
+    at the new state into xq_next at every event.  With `sampled` the rows record the drawn plant.
+    With none of the three it is the plain entry, unchanged."""
     Bt = x.shape[0]
-    more = _trigger_audit_check(task, ws, x, gp_A, sampled, audit) if (sampled is not None or audit is not None) else []
+    more = _trigger_audit_check(task, ws, x, gp_A, sampled, audit) if (sampled is not None or audit is not None or observe is not None) else []
+    obs_t, obs_scalars = _trigger_observe_check(x, observe) if observe is not None else ([], ())
+    _chk(x, *obs_t)
     ls, sf, Adiag, Bh_ = hyper["ls"], hyper["sf"], hyper["Adiag"], hyper["B"]
     _chk(x, *more)
     _chk(x, off, ls, sf, Adiag, Bh_, plan_all, dplan_all, task["plan"], task["dot_plan"], task["centers"], task["tw"], ws["y"],
@@ -1528,8 +1582,11 @@ def unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dpl
     for k in ("tau", "dt_used", "Lfh", "Lh", "xvel", "uBu", "Lkd"):
         if tuple(tws[k].shape) != ((Bt, 3) if k == "Lkd" else (Bt,)):
             raise ValueError("trigger step: output buffer %s of the wrong shape" % k)
-    entry = "bcbf_unicycle_trigger_step_audit" if more else "bcbf_unicycle_trigger_step"
-    tail, keep_more = tuple(_p(v) for v in more), (tuple(more),)
+    entry = "bcbf_unicycle_trigger_step_observe" if observe is not None else ("bcbf_unicycle_trigger_step_audit" if more else "bcbf_unicycle_trigger_step")
+    tail, keep_more = tuple(_p(v) for v in more), (tuple(more), tuple(obs_t))
+    if observe is not None:
+        L_mean, ld, row0, every, flags = obs_scalars
+        tail += (L_mean, _p(obs_t[0]), _p(obs_t[1]), _p(obs_t[2]), ld, row0, every, _p(obs_t[3]), flags)
     fn = getattr(lib, entry + _suf(x))
     args = (_p(x), _p(ws["y"]), _p(ws["status"]), _p(ws["fhat"]), _p(ws["ghat"]), _p(ws["Mk"]), _p(task["centers"]), _p(task["tw"]),
             _p(off), float(r), _p(ls), _p(sf), _p(Adiag), _p(Bh_), float(deltaL), float(zeta), float(L_alpha), float(tau_min),

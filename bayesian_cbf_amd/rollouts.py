@@ -9,6 +9,7 @@ at the end."""
 import math
 import os
 import time
+from types import SimpleNamespace as types_ns
 
 import torch
 
@@ -221,8 +222,7 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     if plant not in ("true", "posterior"):
         raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
     sampled = plant == "posterior"
-    dev = torch.device(device)
-    f = dict(dtype=dtype, device=dev)
+    f = dict(dtype=dtype, device=torch.device(device))
     if gp is not None:
         ti._require_rbf(gp.get("kernel", "rbf"))
         hyper = _trigger_hyper(gp["ell"], gp["s2"], gp["A"], gp["Bm"], Bt, f)
@@ -232,8 +232,35 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
                              "trigger_hyper=dict(ls, sf, A, B)")
         ti._require_rbf(trigger_hyper.get("kernel", "rbf"))
         hyper = _trigger_hyper(trigger_hyper["ls"], trigger_hyper["sf"], trigger_hyper["A"], trigger_hyper["B"], Bt, f)
+    c = _self_triggered_setup("self_triggered_rollouts", Bt, horizon, dt, tau_min, tau_max, max_events, start, goal, start_noise,
+                              max_risk, dtype, device, seed, Nte, off, sampled, audit)
+    ws, task, x = c.ws, c.task, c.x
+    if gp is None:
+        A = torch.diag(torch.tensor(kernel_diag_A, **f)).expand(Bt, 3, 3).contiguous()
+        ws["Mk"].zero_()
+        ws["Bk"].copy_(torch.eye(3, **f).expand(Bt, 3, 3))
+        gp = dict(A=A)
+    solve = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=L_true, L_mean=L_mean, max_iters=max_iters)
+    trigger = ops.unicycle_trigger_step_prepare(task, ws, c.tws, x, c.off, c.r, hyper, c.plan_all, c.dplan_all, dt, horizon, tau_min,
+                                                tau_max, L_true=L_true, deltaL=deltaL, zeta=zeta, L_alpha=L_alpha,
+                                                **(dict(gp_A=gp["A"], sampled=c.draw, audit=c.hold) if c.aws is not None else {}))
+    rec, before, after = _self_triggered_record(c) if record else (None, None, None)
+    c.loop_seconds = _self_triggered_run(c, [lambda: _self_triggered_event(c, solve, trigger)], c.state, use_graph and not record,
+                                         before=before, after=after)
+    return _self_triggered_result(c, rec)
+
+
+def _self_triggered_setup(who, Bt, horizon, dt, tau_min, tau_max, max_events, start, goal, start_noise, max_risk, dtype, device, seed,
+                          Nte, off, sampled, audit):
+    """What the self-triggered loops share before their model enters: the task, the start states (the generator's first draws),
+    the posterior plant's normals (its next), the planner's tables, the test grid, the workspaces and the statistics buffers, as
+    one namespace.  `state`: what an event changes (saved and restored around a graph capture)."""
+    import types
+    from . import trigger_interval as ti
+    dev = torch.device(device)
+    f = dict(dtype=dtype, device=dev)
     if not (0 < tau_min <= tau_max < math.inf) or not horizon > 0:
-        raise ValueError("self_triggered_rollouts: need 0 < tau_min <= tau_max < inf and horizon > 0")
+        raise ValueError("%s: need 0 < tau_min <= tau_max < inf and horizon > 0" % who)
     numSteps = max(3, int(round(horizon / dt)))
     if max_events is None:
         max_events = int(math.ceil(horizon / tau_min))
@@ -245,11 +272,6 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     z_all = torch.randn(max_events, Bt, 3, generator=gen, **f) if sampled else None
     ws = ops.control_workspace(Bt, 2, dtype, dev)
     tws = ops.trigger_workspace(Bt, dtype, dev)
-    if gp is None:
-        A = torch.diag(torch.tensor(kernel_diag_A, **f)).expand(Bt, 3, 3).contiguous()
-        ws["Mk"].zero_()
-        ws["Bk"].copy_(torch.eye(3, **f).expand(Bt, 3, 3))
-        gp = dict(A=A)
     aws = ops.trigger_audit_workspace(Bt, 2, dtype, dev) if (sampled or audit) else None
     draw = aws["sampled"] if sampled else None
     hold = aws["audit"] if audit else None
@@ -267,97 +289,134 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
     act_hist = torch.zeros(max_events, Bt, dtype=torch.bool, device=dev)
     ectr = torch.zeros(1, dtype=torch.long, device=dev)
     t, events = tws["t"], tws["events"]
-    solve = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=L_true, L_mean=L_mean, max_iters=max_iters)
-    trigger = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, dt, horizon, tau_min, tau_max,
-                                                L_true=L_true, deltaL=deltaL, zeta=zeta, L_alpha=L_alpha,
-                                                **(dict(gp_A=gp["A"], sampled=draw, audit=hold) if aws is not None else {}))
-    gam, w_cost = task["gammas"], task["w"]
     state = [x, min_h, cost, fails, t, events, task["plan"], task["dot_plan"], dt_hist, act_hist, ectr]
     if sampled:
         state += [draw["viol"], draw["solved"], draw["min_cbc"]]
     if audit:
         state += [hold[k] for k in ("u_held", "held", "audit_n", "audit_neg", "audit_min")]
-    rec = None
-    if record:
-        rec = dict(x_before=torch.empty(max_events, Bt, 3, **f), u=torch.empty(max_events, Bt, 2, **f),
-                   status=torch.empty(max_events, Bt, dtype=torch.int32, device=dev), tau=torch.empty(max_events, Bt, **f),
-                   dt_used=dt_hist, t=torch.empty(max_events, Bt, dtype=torch.float64, device=dev),
-                   x_after=torch.empty(max_events, Bt, 3, **f), active=act_hist, plan=torch.empty(max_events, Bt, 3, **f),
-                   dot_plan=torch.empty(max_events, Bt, 3, **f), Mk=torch.empty(max_events, Bt, 3, 3, **f),
-                   Bk=torch.empty(max_events, Bt, 3, 3, **f))
-        if sampled:
-            rec.update(z=z_all, xdot_s=torch.empty(max_events, Bt, 3, **f), cbc_s=torch.empty(max_events, Bt, 3, **f))
-        if audit:
-            rec.update(held=torch.empty(max_events, Bt, dtype=torch.int32, device=dev), held_mean=torch.empty(max_events, Bt, 2, **f),
-                       held_margin=torch.empty(max_events, Bt, 2, **f))
+    return types.SimpleNamespace(Bt=Bt, horizon=horizon, tau_min=tau_min, max_events=max_events, max_risk=max_risk, dtype=dtype, dev=dev,
+                                 f=f, gen=gen, xg=xg, task=task, x=x, z_all=z_all, ws=ws, tws=tws, aws=aws, draw=draw, hold=hold, off=off,
+                                 r=r, plan_all=plan_all, dplan_all=dplan_all, min_h=min_h, min_h_prev=torch.empty_like(min_h), cost=cost, cost_prev=cost_prev, fails=fails,
+                                 fails_prev=fails_prev, active=active, dt_hist=dt_hist, act_hist=act_hist, ectr=ectr, t=t, events=events,
+                                 state=state, sampled=sampled, audit=audit)
 
-    def one_event():
-        torch.lt(t, horizon, out=active)          # who takes this event (the trigger step leaves the others alone)
-        solve()                                   # rows -> terms -> SOCP at the current state, no plant
-        if sampled:                               # this event's draws, by the device event counter
-            draw["z"].copy_(z_all.index_select(0, ectr)[0])
-        trigger()                                 # tau, the plant over the time the control is held, clock, planner rows
-        # the bookkeeping of `monte_carlo_safety_rollouts`, per event; an idle instance's cost and failure count are put back
-        # (its min_h cannot change: its state does not)
-        cost_prev.copy_(cost)
-        fails_prev.copy_(fails)
-        ops.rollout_stats(ws["cst"], ws["y"], ws["status"], w_cost, gam, min_h, cost, fails)
-        torch.where(active, cost, cost_prev, out=cost)
-        torch.where(active, fails, fails_prev, out=fails)
-        dt_hist.index_copy_(0, ectr, tws["dt_used"][None])
-        act_hist.index_copy_(0, ectr, active[None])
-        ectr.add_(1)
 
+def _self_triggered_event(c, solve, trigger, freeze_min_h=False):
+    """One event of a self-triggered loop on the buffers of `_self_triggered_setup`: no device read, capturable.
+    freeze_min_h: an idle instance's min_h is put back too.  The bookkeeping launch evaluates h at the state BEFORE the step, so
+    without it the first idle iteration of an instance that finished early adds h of its final state to its minimum -- a state
+    that an instance finishing at the last iteration never has evaluated (`self_triggered_rollouts` keeps that, as it always did)."""
+    ws = c.ws
+    torch.lt(c.t, c.horizon, out=c.active)      # who takes this event (the trigger step leaves the others alone)
+    solve()                                     # rows -> terms -> SOCP at the current state, no plant
+    if c.sampled:                               # this event's draws, by the device event counter
+        c.draw["z"].copy_(c.z_all.index_select(0, c.ectr)[0])
+    trigger()                                   # tau, the plant over the time the control is held, clock, planner rows
+    # the bookkeeping of `monte_carlo_safety_rollouts`, per event; an idle instance's cost and failure count are put back
+    # (its min_h cannot change: its state does not)
+    c.cost_prev.copy_(c.cost)
+    c.fails_prev.copy_(c.fails)
+    if freeze_min_h:
+        c.min_h_prev.copy_(c.min_h)
+    ops.rollout_stats(ws["cst"], ws["y"], ws["status"], c.task["w"], c.task["gammas"], c.min_h, c.cost, c.fails)
+    torch.where(c.active, c.cost, c.cost_prev, out=c.cost)
+    torch.where(c.active, c.fails, c.fails_prev, out=c.fails)
+    if freeze_min_h:
+        torch.where(c.active, c.min_h, c.min_h_prev, out=c.min_h)
+    c.dt_hist.index_copy_(0, c.ectr, c.tws["dt_used"][None])
+    c.act_hist.index_copy_(0, c.ectr, c.active[None])
+    c.ectr.add_(1)
+
+
+def _self_triggered_record(c):
+    """(rec, before(e), after(e)): the per-event record of a self-triggered loop and the two hooks that fill it around an event."""
+    Bt, f, dev, E = c.Bt, c.f, c.dev, c.max_events
+    ws, tws, task, x, draw, hold = c.ws, c.tws, c.task, c.x, c.draw, c.hold
+    rec = dict(x_before=torch.empty(E, Bt, 3, **f), u=torch.empty(E, Bt, 2, **f), status=torch.empty(E, Bt, dtype=torch.int32, device=dev),
+               tau=torch.empty(E, Bt, **f), dt_used=c.dt_hist, t=torch.empty(E, Bt, dtype=torch.float64, device=dev),
+               x_after=torch.empty(E, Bt, 3, **f), active=c.act_hist, plan=torch.empty(E, Bt, 3, **f), dot_plan=torch.empty(E, Bt, 3, **f),
+               Mk=torch.empty(E, Bt, 3, 3, **f), Bk=torch.empty(E, Bt, 3, 3, **f))
+    if c.sampled:
+        rec.update(z=c.z_all, xdot_s=torch.empty(E, Bt, 3, **f), cbc_s=torch.empty(E, Bt, 3, **f))
+    if c.audit:
+        rec.update(held=torch.empty(E, Bt, dtype=torch.int32, device=dev), held_mean=torch.empty(E, Bt, 2, **f),
+                   held_margin=torch.empty(E, Bt, 2, **f))
+
+    def before(e):
+        rec["x_before"][e], rec["plan"][e], rec["dot_plan"][e] = x, task["plan"], task["dot_plan"]
+        if c.audit:
+            rec["held"][e] = hold["held"]
+
+    def after(e):
+        rec["u"][e], rec["Mk"][e], rec["Bk"][e] = ws["y"][:, :2], ws["Mk"], ws["Bk"]
+        rec["status"][e] = ws["status"]
+        rec["tau"][e] = tws["tau"]
+        rec["t"][e] = c.t
+        rec["x_after"][e] = x
+        if c.sampled:
+            rec["xdot_s"][e], rec["cbc_s"][e] = draw["xdot_s"], draw["cbc_s"]
+        if c.audit:
+            rec["held_mean"][e], rec["held_margin"][e] = hold["held_mean"], hold["held_margin"]
+    return rec, before, after
+
+
+def _self_triggered_run(c, event_fns, state, use_graph, which=None, between=None, before=None, after=None):
+    """The max_events iterations of a self-triggered loop; returns the seconds they took.  event_fns: one event closure per set of
+    bound buffers (one for a frozen model; the learning loop has one per operator buffer), which(e) -> the index of the one
+    iteration e runs.  use_graph: every closure is captured once (warm-up on the capture stream, `state` saved and restored around
+    it) and replayed.  between(e): eager work after iteration e (the refits).  before(e) / after(e): the record's hooks (eager)."""
+    dev = c.dev
     torch.cuda.synchronize(dev)
-    graph = None
-    if use_graph and not record:
+    graphs = None
+    if use_graph:
         side = torch.cuda.Stream(device=dev)
         saved = [v.clone() for v in state]
-        with torch.cuda.stream(side):               # warm-up on the capture stream (allocator, lazy module load)
-            one_event()
-        side.synchronize()
-        for dst, src in zip(state, saved):
-            dst.copy_(src)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            one_event()
-        for dst, src in zip(state, saved):
-            dst.copy_(src)
+        graphs = []
+        for fn in event_fns:
+            with torch.cuda.stream(side):               # warm-up on the capture stream (allocator, lazy module load)
+                fn()
+            side.synchronize()
+            for dst, src in zip(state, saved):
+                dst.copy_(src)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                fn()
+            for dst, src in zip(state, saved):
+                dst.copy_(src)
+            graphs.append(graph)
         torch.cuda.synchronize(dev)
     t_loop = time.perf_counter()
-    for e in range(max_events):
-        if graph is not None:
-            graph.replay()
-            continue
-        if record:
-            rec["x_before"][e], rec["plan"][e], rec["dot_plan"][e] = x, task["plan"], task["dot_plan"]
-            if audit:
-                rec["held"][e] = hold["held"]
-        one_event()
-        if record:
-            rec["u"][e], rec["Mk"][e], rec["Bk"][e] = ws["y"][:, :2], ws["Mk"], ws["Bk"]
-            rec["status"][e] = ws["status"]
-            rec["tau"][e] = tws["tau"]
-            rec["t"][e] = t
-            rec["x_after"][e] = x
-            if sampled:
-                rec["xdot_s"][e], rec["cbc_s"][e] = draw["xdot_s"], draw["cbc_s"]
-            if audit:
-                rec["held_mean"][e], rec["held_margin"][e] = hold["held_mean"], hold["held_margin"]
+    for e in range(c.max_events):
+        k = which(e) if which is not None else 0
+        if graphs is not None:
+            graphs[k].replay()
+        else:
+            if before is not None:
+                before(e)
+            event_fns[k]()
+            if after is not None:
+                after(e)
+        if between is not None:
+            between(e)
     torch.cuda.synchronize(dev)
-    t_loop = time.perf_counter() - t_loop
-    collided = ~(min_h >= 0)
-    per_event_cost = cost / events.clamp(min=1).to(dtype)
-    stats = reduce_rollout_stats(collided.sum(), min_h.min(), per_event_cost.sum(), (fails > 0).sum(), Bt)
-    taken = dt_hist[act_hist]
+    return time.perf_counter() - t_loop
+
+
+def _self_triggered_result(c, rec):
+    """The statistics every self-triggered loop returns (see `self_triggered_rollouts`)."""
+    Bt, f, x, t, events, draw, hold = c.Bt, c.f, c.x, c.t, c.events, c.draw, c.hold
+    collided = ~(c.min_h >= 0)
+    per_event_cost = c.cost / events.clamp(min=1).to(c.dtype)
+    stats = reduce_rollout_stats(collided.sum(), c.min_h.min(), per_event_cost.sum(), (c.fails > 0).sum(), Bt)
+    taken = c.dt_hist[c.act_hist]
     dt_used = dict(min=float(taken.min()), median=float(taken.median()), max=float(taken.max())) if taken.numel() else None
-    at_min = float((taken == torch.tensor(tau_min, **f)).double().mean()) if taken.numel() else None
-    out = dict(stats=stats, x_final=x, t=t, events=events, events_per_second=events.double() / t, done=float((t >= horizon).double().mean()),
-               dt_used=dt_used, min_h=min_h, dist_to_goal=(x[:, :2] - xg[:2]).norm(dim=1), loop_seconds=t_loop, task=task, rec=rec,
+    at_min = float((taken == torch.tensor(c.tau_min, **f)).double().mean()) if taken.numel() else None
+    out = dict(stats=stats, x_final=x, t=t, events=events, events_per_second=events.double() / t, done=float((t >= c.horizon).double().mean()),
+               dt_used=dt_used, min_h=c.min_h, dist_to_goal=(x[:, :2] - c.xg[:2]).norm(dim=1), loop_seconds=c.loop_seconds, task=c.task, rec=rec,
                share_at_tau_min=at_min)
-    if sampled:
-        out["risk"] = reduce_risk_stats(draw["solved"].sum(), draw["viol"].sum(0), draw["min_cbc"].min(0).values, max_risk)
-    if audit:
+    if c.sampled:
+        out["risk"] = reduce_risk_stats(draw["solved"].sum(), draw["viol"].sum(0), draw["min_cbc"].min(0).values, c.max_risk)
+    if c.audit:
         n = int(hold["audit_n"].sum())
         neg = hold["audit_neg"].sum(0).tolist()                        # [Kob][mean, margin]
         mins = hold["audit_min"].min(0).values.double().tolist()
@@ -365,6 +424,133 @@ def self_triggered_rollouts(Bt, horizon=10.0, dt=0.05, gp=None, trigger_hyper=No
         out["audit"] = dict(events=n, neg_mean=[int(v[0]) for v in neg], neg_margin=[int(v[1]) for v in neg],
                             rate_mean=sum(v[0] for v in neg) / max(n * rows, 1), rate_margin=sum(v[1] for v in neg) / max(n * rows, 1),
                             min_mean=[float(v[0]) for v in mins], min_margin=[float(v[1]) for v in mins])
+    return out
+
+
+def self_triggered_learning_rollouts(Bt, horizon=10.0, dt=0.05, max_train=512, refit_every=40, obs_every=1, tau_min=1e-3, tau_max=0.05,
+                                     max_events=None, L_mean=1.0, L_true=12.0, retry_levels=3, min_jitter_level=1e-5, level_decay_every=4,
+                                     start=(-3.0, -1.0, -math.pi / 4), goal=(0.0, 0.0, math.pi / 4), start_noise=0.05, max_risk=0.01,
+                                     dtype=torch.float64, device="cuda", seed=0, record=False, max_iters=30, use_graph=False, Nte=1e3,
+                                     off=None, deltaL=1e-4, zeta=1e-2, L_alpha=1.0, plant="true", audit=False):
+    """The self-triggered closed loop that LEARNS ITS DYNAMICS ONLINE: the two halves of the paper's algorithm in one loop, as the
+    reference's controller runs them (unicycle_move_to_pose.py:326-386, :970-978).  The events are those of
+    `self_triggered_rollouts` -- same task, start states for the same seed, planner, trigger and statistics -- on a model that is
+    refitted from the loop's own (x_e, u_e, x_{e+1}) rows with the host-free refits of `self_learning_closed_loop`.
+    Start model: `synthetic.make_instances(Bt, max_train, 3, 2, variant="theta")`, one GP per instance; the trigger bound reads its
+    ell, s2, A, Bm, which stay as they are (no hyper-parameter fit here).  The prior mean is AckermannDrive(L_mean) against a true
+    wheelbase L_true, so there is a residual to learn.
+    One EVENT: the solve with dt = 0 at the shift-invariant query xq = (0, 0, theta) (bcbf_unicycle_control_step_observe), the
+    OBSERVING trigger step (bcbf_unicycle_trigger_step_observe: tau, the hold dt_b on the plant, the clock, the event as an
+    observation row with ITS OWN dt_b, and xq at the new state) and the bookkeeping.  Stream layout, per instance: rows
+    0 .. max_train - 1 the synthetic start, row max_train + e // obs_every the observation of event e when e % obs_every == 0.
+    Live instances take events in lockstep, so after iteration e each of them has written 1 + e // obs_every rows; an instance
+    that has reached the horizon writes no more, and the rows it never writes stay the plant at rest (`ops.trigger_observe_workspace`),
+    true and uninformative.  When (e + 1) % refit_every == 0 the last max_train stream rows are refactored
+    (`ops.refit_with_retries` + `ops.potrs`, a fresh level * rand jitter per factorisation, an instance starting at the level that
+    last worked and going one level down every `level_decay_every`-th refit, never below `min_jitter_level`: the rules of
+    `self_learning_closed_loop`) into the operator buffer that is not being read, and the buffers swap; nothing waits for the
+    host.  use_graph: one captured event per operator buffer, the refits launched eagerly between the replays (ignored with record).
+    plant="posterior" is refused: learning from draws of the model's own posterior teaches nothing.  audit: as in
+    `self_triggered_rollouts`.  Once an instance has reached the horizon none of its statistics changes any more, min_h included
+    (it is the minimum over the states at which the instance took an event).
+    Returns what `self_triggered_rollouts` returns, and
+      learning = dict(refits, refit_failures_after_retries, instances_factored_per_retry_level, jitter_level_max, rows_written[Bt],
+                      window, obs_every);
+      final = dict(rows = [dict(X, UH, Y, jitter)] ([Bt, max_train, .]: the raw rows the final model holds, with the jitter they were
+              factored with), bounds = [(0, Bt)], hyper, posterior = (Mk, Bk) of the final model at xq_check, xq_check, window_lo (the
+              stream row the window starts at), stream_rows = dict(X, UH, Y, row0)) -- the layout of `self_learning_closed_loop`'s;
+      with record, rec gains obs_x, obs_uh, obs_y (the stream row of index max_train + e // obs_every after event e: this event's
+      where e % obs_every == 0 and the instance was active, else an older or the rest row), xq (the query of the event's solve) and
+      the running statistics cost, fails, min_h after the event."""
+    from .synthetic import make_instances
+    if plant != "true":
+        raise ValueError("self_triggered_learning_rollouts: plant must be 'true' (got %r): learning from draws of the model's own "
+                         "posterior teaches nothing" % (plant,))
+    if max_train < 1 or refit_every < 1 or obs_every < 1:
+        raise ValueError("self_triggered_learning_rollouts: need max_train >= 1, refit_every >= 1, obs_every >= 1")
+    c = _self_triggered_setup("self_triggered_learning_rollouts", Bt, horizon, dt, tau_min, tau_max, max_events, start, goal,
+                              start_noise, max_risk, dtype, device, seed, Nte, off, False, audit)
+    f, dev, ws, task, x, W, E = c.f, c.dev, c.ws, c.task, c.x, max_train, c.max_events
+    p = make_instances(Bt, W, 3, 2, dtype=dtype, device=dev, seed=seed, variant="theta")
+    hp = {k: p[k] for k in ("ell", "s2", "Bm", "M0", "A")}
+    hyper = _trigger_hyper(hp["ell"], hp["s2"], hp["A"], hp["Bm"], Bt, f)
+    # the observation stream: the synthetic start, then one row per observed event
+    ow = ops.trigger_observe_workspace(Bt, W + (E + obs_every - 1) // obs_every, dtype, dev)
+    Xall, UHall, Yall = ow["obs"]
+    Xall[:, :W], UHall[:, :W], Yall[:, :W] = p["X"], p["UH"], p["Xdot"]
+    xq = ow["xq_next"]
+    xq.copy_(x)
+    xq[:, :2] = 0
+    ow.update(row0=W, every=obs_every, L_mean=L_mean)
+    E_ = ops.lop_elems(W, dtype)
+    mk = lambda: dict(Lop=torch.empty(Bt, E_, **f), UHB=torch.empty(Bt, W, 3, **f), Vw=torch.empty(Bt, W, 3, **f), X=torch.empty(Bt, W, 3, **f))
+    bufs = [mk(), mk()]
+    info, info2 = (torch.zeros(Bt, dtype=torch.int32, device=dev) for _ in range(2))
+    fail_count = torch.zeros((), dtype=torch.int64, device=dev)
+    level = torch.full((Bt,), float(min_jitter_level), **f)          # make_psd's level per instance (x10 per failed attempt)
+    retry_counts = torch.zeros(retry_levels + 1, dtype=torch.int64, device=dev)
+    L = types_ns(cur=0, refits=0, lo=0, J=p["jitter"].clone())
+
+    def factor_into(buf, Xw, UHw, Yw, Jw):
+        ops.refit_with_retries(Xw, UHw, hp["Bm"], hp["ell"], hp["s2"], Jw, (buf["Lop"], buf["UHB"], info), levels=retry_levels,
+                               scratch=info2, level=level, counts=retry_counts)
+        ops.potrs(buf["Lop"], Yw, UHw, hp["M0"], want_alpha=False, out_Vw=buf["Vw"])
+        buf["X"].copy_(Xw)
+        fail_count.add_((info != 0).sum())
+
+    factor_into(bufs[0], p["X"], p["UH"], p["Xdot"], L.J)
+    for k, v in bufs[0].items():                                   # (both buffers hold a model from the start: a graph is captured on each)
+        bufs[1][k].copy_(v)
+    solves = [ops.unicycle_control_step_prepare(dict(b_, **hp), task, ws, x, dt=0.0, L_true=L_true, L_mean=L_mean, max_iters=max_iters,
+                                                observe=dict(xq=xq, xq_next=None, shift_invariant=True)) for b_ in bufs]
+    trigger = ops.unicycle_trigger_step_prepare(task, ws, c.tws, x, c.off, c.r, hyper, c.plan_all, c.dplan_all, dt, horizon, tau_min,
+                                                tau_max, L_true=L_true, deltaL=deltaL, zeta=zeta, L_alpha=L_alpha, gp_A=hp["A"],
+                                                audit=c.hold, observe=ow)
+
+    def between(e):
+        """After iteration e: every `refit_every`-th time, refactor the last W stream rows into the buffer that is not being read."""
+        if (e + 1) % refit_every:
+            return
+        lo = 1 + e // obs_every                                     # live instances have written rows W .. W + e // obs_every
+        cut = lambda t_: t_[:, lo:lo + W].contiguous()
+        L.refits += 1
+        if level_decay_every and L.refits % level_decay_every == 0:
+            level.div_(10).clamp_(min=float(min_jitter_level))
+        # a fresh jitter draw per factorisation, at the instance's level: one below the one that last worked (make_psd, :903-919)
+        Jw = (level[:, None] * torch.rand(Bt, W, generator=c.gen, **f)).contiguous()
+        factor_into(bufs[1 - L.cur], cut(Xall), cut(UHall), cut(Yall), Jw)
+        L.cur, L.lo, L.J = 1 - L.cur, lo, Jw
+
+    rec, before, after = None, None, None
+    if record:
+        rec, before0, after0 = _self_triggered_record(c)
+        rec.update(obs_x=torch.empty(E, Bt, 3, **f), obs_uh=torch.empty(E, Bt, 3, **f), obs_y=torch.empty(E, Bt, 3, **f),
+                   xq=torch.empty(E, Bt, 3, **f), cost=torch.empty(E, Bt, **f), fails=torch.empty(E, Bt, dtype=torch.int32, device=dev),
+                   min_h=torch.empty(E, Bt, **f))
+
+        def before(e):
+            before0(e)
+            rec["xq"][e] = xq
+
+        def after(e):
+            after0(e)
+            row = W + e // obs_every
+            rec["obs_x"][e], rec["obs_uh"][e], rec["obs_y"][e] = Xall[:, row], UHall[:, row], Yall[:, row]
+            rec["cost"][e], rec["fails"][e], rec["min_h"][e] = c.cost, c.fails, c.min_h
+    state = c.state + [Xall, UHall, Yall, xq]
+    c.loop_seconds = _self_triggered_run(c, [lambda s_=s_: _self_triggered_event(c, s_, trigger, freeze_min_h=True) for s_ in solves], state,
+                                         use_graph and not record, which=lambda e: L.cur, between=between, before=before, after=after)
+    out = _self_triggered_result(c, rec)
+    out["learning"] = dict(refits=L.refits, refit_failures_after_retries=int(fail_count),
+                           instances_factored_per_retry_level=[int(v) for v in retry_counts.tolist()], jitter_level_max=float(level.max()),
+                           rows_written=(c.events + (obs_every - 1)) // obs_every, window=W, obs_every=obs_every)
+    b_ = bufs[L.cur]
+    Mk, Bk = ops.posterior_step(b_["Lop"], b_["Vw"], b_["X"], b_["UHB"], hp["ell"], hp["s2"], hp["Bm"], hp["M0"], p["xq"])
+    sl = slice(L.lo, L.lo + W)
+    out["final"] = dict(rows=[dict(X=Xall[:, sl].clone(), UH=UHall[:, sl].clone(), Y=Yall[:, sl].clone(), jitter=L.J.clone())],
+                        bounds=[(0, Bt)], hyper={k: v.clone() for k, v in hp.items()}, posterior=(Mk, Bk), xq_check=p["xq"],
+                        window_lo=L.lo, stream_rows=dict(X=Xall, UH=UHall, Y=Yall, row0=W))
+    torch.cuda.synchronize(dev)
     return out
 
 

@@ -7,6 +7,7 @@ over the GPUs of one node (contiguous shard per rank, no collective inside the l
     python examples_mc_rollouts.py --plant posterior --max-risk 0.05 --graph     # plants drawn from the model's posterior: `risk`
     python examples_mc_rollouts.py --trigger self --tau-min 1e-3 --tau-max 0.05 --compare-periodic --graph   # the loop that acts on tau
     python examples_mc_rollouts.py --trigger self --plant posterior --audit --max-risk 0.05 --graph   # ... on drawn plants: `risk`, `audit`
+    python examples_mc_rollouts.py --trigger self --learn --max-train 512 --refit-every 40 --audit --compare-periodic --graph   # ... that learns online
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         examples_mc_rollouts.py --gpus 8 --trajectories 32768 --steps 200
 
@@ -28,10 +29,12 @@ if ROOT not in sys.path:
 
 def self_triggered(args, ctx, gp, dtype, n_loc):
     """--trigger self: `rollouts.self_triggered_rollouts` over the horizon the periodic loop covers (steps x its dt = 0.05)."""
-    from bayesian_cbf_amd.rollouts import monte_carlo_safety_rollouts, self_triggered_rollouts
+    from bayesian_cbf_amd.rollouts import monte_carlo_safety_rollouts, self_triggered_learning_rollouts, self_triggered_rollouts
     if ctx.world != 1:
         sys.exit("--trigger self runs on one GPU")
     dt = 0.05
+    if args.learn:
+        return self_triggered_learning(args, ctx, dtype, n_loc, dt)
     hyper = None
     if gp is None:      # the fixed-kernel model has no data kernel: unit lengthscales and scale, its A and B
         hyper = dict(ls=[1.0, 1.0, 1.0], sf=1.0, A=torch.diag(torch.tensor([1e-2, 1e-2, 1e-2], dtype=torch.float64)), B=torch.eye(3))
@@ -58,6 +61,33 @@ def self_triggered(args, ctx, gp, dtype, n_loc):
         print(json.dumps(line))
 
 
+def self_triggered_learning(args, ctx, dtype, n_loc, dt):
+    """--trigger self --learn: `rollouts.self_triggered_learning_rollouts`, the self-triggered loop on a model it refits from its own
+    rows (start model: synthetic, --max-train points per trajectory; prior wheelbase 1 against a true 12)."""
+    from bayesian_cbf_amd.rollouts import monte_carlo_safety_rollouts, self_triggered_learning_rollouts
+    if args.plant != "true" or args.learned or args.shared_learned:
+        sys.exit("--learn starts from its own model and learns on the true plant: drop --plant posterior / --learned / --shared-learned")
+    out = self_triggered_learning_rollouts(n_loc, horizon=args.steps * dt, dt=dt, max_train=args.max_train, refit_every=args.refit_every,
+                                           obs_every=args.obs_every, tau_min=args.tau_min, tau_max=args.tau_max, max_risk=args.max_risk,
+                                           seed=ctx.rank, dtype=dtype, device=ctx.device, use_graph=args.graph, zeta=args.zeta, audit=args.audit)
+    ev = out["events"].double()
+    lr = out["learning"]
+    line = dict(config="c4 self-triggered, learning online", trajectories=n_loc, horizon=args.steps * dt, tau_min=args.tau_min,
+                tau_max=args.tau_max, zeta=args.zeta, done=out["done"], events_mean=float(ev.mean()), events_max=int(ev.max()),
+                events_per_second_mean=float(out["events_per_second"].mean()), periodic_events=args.steps, dt_used=out["dt_used"],
+                loop_seconds=out["loop_seconds"], share_of_events_at_tau_min=out["share_at_tau_min"], **out["stats"],
+                learning=dict(lr, rows_written=dict(min=int(lr["rows_written"].min()), max=int(lr["rows_written"].max()))))
+    if args.audit:
+        line["audit"] = out["audit"]
+    if args.compare_periodic:
+        per = monte_carlo_safety_rollouts(n_loc, numSteps=args.steps, dt=dt, gp=None, max_risk=args.max_risk, seed=ctx.rank, dtype=dtype,
+                                          device=ctx.device, use_graph=args.graph)
+        line["periodic"] = dict(per["stats"], loop_seconds=per["loop_seconds"], events_per_second=1.0 / dt,
+                                model="fixed kernel (the periodic Monte-Carlo loop does not learn)")
+    if ctx.rank == 0:
+        print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -74,6 +104,12 @@ def main():
     ap.add_argument("--audit", action="store_true",
                     help="--trigger self: look at every held control again where it is released (mean and margin of each obstacle "
                          "condition under it at the next event's state); the JSON line gains `audit`")
+    ap.add_argument("--learn", action="store_true",
+                    help="--trigger self: the loop refits its model from its own (x, u, x_next) rows (self_triggered_learning_rollouts); "
+                         "the JSON line gains `learning`")
+    ap.add_argument("--max-train", type=int, default=512, help="--learn: rows of the sliding window a refit learns from")
+    ap.add_argument("--refit-every", type=int, default=40, help="--learn: events between refits")
+    ap.add_argument("--obs-every", type=int, default=1, help="--learn: every how many events an observation row is written")
     ap.add_argument("--tau-min", type=float, default=1e-3)
     ap.add_argument("--tau-max", type=float, default=0.05)
     ap.add_argument("--zeta", type=float, default=1e-2, help="--trigger self: the safety margin zeta of the trigger time")

@@ -262,6 +262,50 @@ int bcbf_unicycle_trigger_step_audit_f64(double* x, const double* y, const int* 
                                          double* held_mean, double* held_margin, int* audit_n, int* audit_neg, double* audit_min,
                                          int Bt, int Bh, int Kob, int Nte, int P, void* stream);
 
+/* bcbf_unicycle_trigger_step_audit that also OBSERVES the event for a learner: the same launch, every argument of that entry
+ * with unchanged meaning (groups P and H stay optional), and after the plant step one more piece of work for the same thread,
+ * plain stores from one lane, no atomics.  It is what lets the self-triggered loop learn its dynamics online: the periodic
+ * observing entry (bcbf_unicycle_control_step_observe) writes its row with the plant step of the SOLVE launch and divides by one
+ * dt for the batch; here the solve runs with dt = 0 and every instance holds its control for its own dt_b.
+ * Everything the audit entry writes is bit-identical to that entry's on the same inputs.  A finished instance (t[b] >= t_end)
+ * leaves before anything of it is read or written, the new buffers included.
+ *  Group O, the observation -- rows present when obs_x is non-NULL (then obs_uh and obs_y are), xq_next independent of them:
+ *   obs_x, obs_uh, obs_y [Bt, obs_ld, 3]: the observation STREAM of every instance.  With e = events[b] BEFORE the increment:
+ *   if e % obs_every == 0 and k = obs_row0 + e / obs_every < obs_ld, row b * obs_ld + k is written; a row with k >= obs_ld is
+ *   skipped silently, nothing is written outside the buffers.  The index comes from the device counter, so one captured graph
+ *   serves every event and instances whose counts differ write their own rows.  The row is that of
+ *   bcbf_unicycle_control_step_observe (LearnedShiftInvariantDynamics.train, unicycle_move_to_pose.py:326-372) with the event's
+ *   own hold dt_b, as the working type stores it (dt_used[b]), in place of dt:
+ *     obs_x  = the state before the step, (0, 0, theta) with flags bit 0 (shift-invariant inputs)
+ *     obs_uh = (1, u)
+ *     obs_y  = (x_new - x_old) / dt_b - g(theta; L_mean) u      from the states as stored (rounded to the working type);
+ *   an unsolved instance kept its state: obs_uh = (1, 0, 0), obs_y = 0 -- a unicycle at rest.  With group P the row records the
+ *   drawn plant (x_new is the state that step stored).  L_mean, the wheelbase of the prior mean AckermannDrive, is a float in
+ *   both precisions and is converted to the working type.
+ *   xq_next[Bt,3] (optional): the regressor's input at the NEW state -- (0, 0, theta_new) with flags bit 0 -- the query of the
+ *   next solve; written at every event of a live instance, observed or not.
+ * Limits: those of bcbf_unicycle_trigger_step_audit; the three row buffers together or not at all; with rows obs_ld >= 1,
+ * obs_row0 >= 0, obs_every >= 1 and L_mean a number other than 0; no flag but bit 0; otherwise BCBF_EINVAL before any HIP call,
+ * reason in bcbf_last_error.  No allocation, no host synchronisation: capturable. */
+int bcbf_unicycle_trigger_step_observe_f32(float* x, const float* y, const int* status, const float* fhat, const float* ghat,
+        const float* Mk, const float* centers, const float* tw, const float* off, double r, const float* ls, const float* sf, const float* Adiag,
+        const float* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, double tau_max, double t_end, float L_true,
+        const float* plan_all, const float* dplan_all, double dt_plan, double* t, int* events, float* plan, float* dot_plan, float* tau,
+        float* dt_used, float* Lfh, float* Lkd, float* Lh, float* xvel, float* uBu, const float* Bk, const float* A, const float* grad, const float* cst,
+        const float* sign, const float* rho, const float* z, float* xdot_s, float* cbc_s, int* viol, int* solved, float* min_cbc, float* u_held,
+        int* held, float* held_mean, float* held_margin, int* audit_n, int* audit_neg, float* audit_min, float L_mean, float* obs_x,
+        float* obs_uh, float* obs_y, int obs_ld, int obs_row0, int obs_every, float* xq_next, int flags, int Bt, int Bh, int Kob, int Nte,
+        int P, void* stream);
+int bcbf_unicycle_trigger_step_observe_f64(double* x, const double* y, const int* status, const double* fhat, const double* ghat,
+        const double* Mk, const double* centers, const double* tw, const double* off, double r, const double* ls, const double* sf, const double* Adiag,
+        const double* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, double tau_max, double t_end, double L_true,
+        const double* plan_all, const double* dplan_all, double dt_plan, double* t, int* events, double* plan, double* dot_plan, double* tau,
+        double* dt_used, double* Lfh, double* Lkd, double* Lh, double* xvel, double* uBu, const double* Bk, const double* A, const double* grad, const double* cst,
+        const double* sign, const double* rho, const double* z, double* xdot_s, double* cbc_s, int* viol, int* solved, double* min_cbc, double* u_held,
+        int* held, double* held_mean, double* held_margin, int* audit_n, int* audit_neg, double* audit_min, float L_mean, double* obs_x,
+        double* obs_uh, double* obs_y, int obs_ld, int obs_row0, int obs_every, double* xq_next, int flags, int Bt, int Bh, int Kob, int Nte,
+        int P, void* stream);
+
 /* K2 on a caller-supplied dense SPD matrix (lower triangle of Kb[Bt,N,N] is read): same outputs.
  * Replaces torch.linalg.cholesky (control_affine_model.py:911). */
 int bcbf_potrf_f32(const float* Kb, float* Lop, float* Ldense, int* info, int Bt, int N, void* stream);

@@ -17,7 +17,15 @@ the medians reported (all nine figures are kept).
 
 times, in the same alternating scheme, the plain trigger step against bcbf_unicycle_trigger_step_audit on the same inputs (the plant
 drawn from the posterior with its risk counters, the audit of the held control, or both, as the flags say) and nothing else: the
-medians of three, all six figures, and the plain step's own run-to-run spread (max - min over its three) beside the difference."""
+medians of three, all six figures, and the plain step's own run-to-run spread (max - min over its three) beside the difference.
+
+    python tools/bench_self_triggered.py --observe [--max-train 512] [--refit-every 20] [--out profiles/self_triggered_learning.json]
+
+times, in the same alternating scheme, bcbf_unicycle_trigger_step_audit with no optional group against
+bcbf_unicycle_trigger_step_observe with group O alone (every instance writes a row and its next query at every launch), then the
+loop that learns (`rollouts.self_triggered_learning_rollouts` at --max-train points per instance, eager): one whole learning event
+(posterior at the query, solve, observing trigger step, bookkeeping) from a run without refits, and one refit period
+(--refit-every events and the refit that ends it) from a run with two; each run is made twice and the second is kept."""
 import argparse
 import json
 import math
@@ -33,6 +41,67 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from _timing import timeit  # noqa: E402
 
 
+def observe_timings(args, ops, task, ws, tws, x, off, r, hyper, plan_all, dplan_all, A, L_true, L_mean, dtype):
+    """--observe, one precision: the two entries on the inputs of the other modes, then the loop that learns."""
+    import ctypes
+    from bayesian_cbf_amd import _lib
+    from bayesian_cbf_amd.rollouts import self_triggered_learning_rollouts
+    Bt, Nte, P = x.shape[0], off.shape[0], plan_all.shape[0]
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    fn = getattr(_lib.lib, "bcbf_unicycle_trigger_step_audit" + ("_f64" if dtype == torch.float64 else "_f32"))
+    bound = (p(x), p(ws["y"]), p(ws["status"]), p(ws["fhat"]), p(ws["ghat"]), p(ws["Mk"]), p(task["centers"]), p(task["tw"]), p(off), float(r),
+             p(hyper["ls"]), p(hyper["sf"]), p(hyper["Adiag"]), p(hyper["B"]), 1e-4, 1e-2, 1.0, 1e-9, 1e-6, 1e9, float(L_true), p(plan_all),
+             p(dplan_all), 0.05, p(tws["t"]), p(tws["events"]), p(task["plan"]), p(task["dot_plan"]),
+             *[p(tws[k]) for k in ("tau", "dt_used", "Lfh", "Lkd", "Lh", "xvel", "uBu")], p(ws["Bk"]), p(A), p(ws["grad"]), p(ws["cst"]),
+             p(task["sign"]), p(task["rho"]), *([None] * 13), Bt, hyper["ls"].shape[0], 2, Nte, P)
+
+    def audit_no_group():
+        rc = fn(*bound, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, _lib.lib.bcbf_last_error().decode()
+
+    # every launch is an observed event: the row index stays inside the stream over all timed launches (3 x (warm-up + reps) each)
+    ow = ops.trigger_observe_workspace(Bt, 64, dtype, "cuda")
+    ow.update(every=1 << 20, L_mean=L_mean)
+    observing = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, 0.05, 1e9, 1e-9, 1e-6, L_true=L_true,
+                                                  gp_A=A, observe=ow)
+    tws["events"].zero_()
+
+    def observe_row0():
+        tws["events"].zero_()                   # (one small fill per launch, in both timed forms, so that e % every == 0: a row is written)
+        observing()
+
+    def audit_row0():
+        tws["events"].zero_()
+        audit_no_group()
+
+    audit_row0()
+    observe_row0()
+    torch.cuda.synchronize()
+    ok = ws["status"] == 0                      # (a solved instance's row holds its control; the streams start with u = 0)
+    rows_written = bool((ow["obs"][1][:, 0, 1:][ok] == ws["y"][:, :2][ok]).all()) and bool((ow["xq_next"][:, 2] == x[:, 2]).all())
+    runs = [[timeit(f_, reps=args.reps) for f_ in (audit_row0, observe_row0)] for _ in range(3)]      # alternating; the medians count
+    audit_ms, obs_ms = (sorted(col)[1] for col in zip(*runs))
+    audit_runs = [q[0] for q in runs]
+    out = dict(audit_entry_no_group_ms=audit_ms, observing_trigger_step_ms=obs_ms, added_ms=obs_ms - audit_ms, added_over_audit=obs_ms / audit_ms - 1.0,
+               audit_spread_ms=max(audit_runs) - min(audit_runs), every_instance_wrote_its_row=rows_written,
+               alternating_runs_ms=dict(audit_entry=audit_runs, observe_entry=[q[1] for q in runs]),
+               note="both forms zero the event counters before the launch (one small fill) so that every timed launch is an observed event")
+    # the loop that learns: events without refits, then two refit periods
+    R, W = args.refit_every, args.max_train
+    kw = dict(horizon=100.0, dt=0.05, max_train=W, tau_min=1e-3, tau_max=0.05, dtype=dtype, device="cuda", Nte=args.Nte)
+    for _ in range(2):
+        ev = self_triggered_learning_rollouts(Bt, refit_every=10 * R, max_events=2 * R, **kw)
+    for _ in range(2):
+        per = self_triggered_learning_rollouts(Bt, refit_every=R, max_events=2 * R, **kw)
+    event_ms = ev["loop_seconds"] / (2 * R) * 1e3
+    period_ms = per["loop_seconds"] / 2 * 1e3
+    out.update(max_train=W, refit_every=R, learning_event_eager_ms=event_ms, refit_period_ms=period_ms, refit_ms=period_ms - R * event_ms,
+               refits_in_timed_run=per["learning"]["refits"], refit_failures_after_retries=per["learning"]["refit_failures_after_retries"],
+               instances_factored_per_retry_level=per["learning"]["instances_factored_per_retry_level"],
+               solved_share_last_event=float((ws["status"] == 0).double().mean()))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=4096)
@@ -41,11 +110,19 @@ def main():
     ap.add_argument("--plant", choices=["true", "posterior"], default="true",
                     help="posterior: time the trigger step on the posterior-drawn plant against the plain one (with --audit: both groups)")
     ap.add_argument("--audit", action="store_true", help="time the trigger step with the held-control audit against the plain one")
-    ap.add_argument("--out", default=None, help="default profiles/self_triggered.json, or self_triggered_posterior.json with --plant posterior / --audit")
+    ap.add_argument("--observe", action="store_true",
+                    help="time the observing trigger step against the audit entry with no group, a whole learning event and a refit period")
+    ap.add_argument("--max-train", type=int, default=512, help="--observe: points per instance of the loop that learns")
+    ap.add_argument("--refit-every", type=int, default=20, help="--observe: events per refit period")
+    ap.add_argument("--out", default=None, help="default profiles/self_triggered.json, self_triggered_posterior.json with --plant posterior / --audit, "
+                                                "self_triggered_learning.json with --observe")
     args = ap.parse_args()
     compare_new = args.plant == "posterior" or args.audit
+    if args.observe and compare_new:
+        sys.exit("--observe times group O alone: drop --plant posterior / --audit")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "self_triggered_posterior.json" if compare_new else "self_triggered.json")
+        args.out = os.path.join(ROOT, "profiles", "self_triggered_learning.json" if args.observe else
+                                "self_triggered_posterior.json" if compare_new else "self_triggered.json")
     if not torch.cuda.is_available():
         sys.exit("bench_self_triggered needs the GPU: nothing is measured without it")
     from bayesian_cbf_amd import ops
@@ -56,7 +133,7 @@ def main():
     Nte, Bt = grid.shape[0], args.B
     r = ti._grid_norm(grid)
     res = dict(B=Bt, Nte=Nte, device=torch.cuda.get_device_name(0), reps=args.reps)
-    if not compare_new:
+    if not compare_new and not args.observe:
         res["pair_part_alone_ms_f32_recorded"] = 0.372            # profiles/trigger_interval.json, the only figure measured before
     L_true, L_mean, dt_ref = 12.0, 1.0, 0.01
     for dtype, name in ((torch.float32, "f32"), (torch.float64, "f64")):
@@ -84,6 +161,10 @@ def main():
         plan_all, dplan_all = task["plan"][:1].expand(P, 3).contiguous(), task["dot_plan"][:1].expand(P, 3).contiguous()
         fused = ops.unicycle_trigger_step_prepare(task, ws, tws, x, off, r, hyper, plan_all, dplan_all, 0.05, 1e9, 1e-9, 1e-6,
                                                   L_true=L_true)
+        if args.observe:
+            res[name] = observe_timings(args, ops, task, ws, tws, x, off, r, hyper, plan_all, dplan_all, gp["A"], L_true, L_mean, dtype)
+            print(json.dumps({name: res[name]}))
+            continue
         if compare_new:
             aws = ops.trigger_audit_workspace(Bt, 2, dtype, "cuda")
             aws["sampled"]["z"].copy_(torch.randn(Bt, 3, generator=gen, **f))
