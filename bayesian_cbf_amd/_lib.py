@@ -41,6 +41,11 @@ _SIGS = {
                                                + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
                                                + [c_int] * 3 + [P] * 3),
 }
+# the trigger-step entries: the event's 35 arguments, the 19 of the audit group, the 9 of the observe group, (Bt, Bh, Kob, Nte, P, stream)
+_TS_EVENT = [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11
+_TS_AUDIT = [P] * 19
+_TS_OBSERVE = [c_float, P, P, P, c_int, c_int, c_int, P, c_int]
+_TS_SIZES = [c_int] * 5 + [P]
 _TSIGS = {
     "bcbf_kb_build": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_kb_build_matern52": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
@@ -60,11 +65,9 @@ _TSIGS = {
     "bcbf_potrf": [P, P, P, P, c_int, c_int, P],
     "bcbf_subsample_rows": [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P],
     "bcbf_trigger_interval": [P] * 8 + [c_double] * 4 + [P, P, P, c_int, c_int, c_int, c_int, P],
-    "bcbf_unicycle_trigger_step": [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11 + [c_int] * 5 + [P],
-    "bcbf_unicycle_trigger_step_audit": [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11 + [P] * 19
-                                        + [c_int] * 5 + [P],
-    "bcbf_unicycle_trigger_step_observe": [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11 + [P] * 19
-                                          + [c_float, P, P, P, c_int, c_int, c_int, P, c_int] + [c_int] * 5 + [P],
+    "bcbf_unicycle_trigger_step": _TS_EVENT + _TS_SIZES,
+    "bcbf_unicycle_trigger_step_audit": _TS_EVENT + _TS_AUDIT + _TS_SIZES,
+    "bcbf_unicycle_trigger_step_observe": _TS_EVENT + _TS_AUDIT + _TS_OBSERVE + _TS_SIZES,
     "bcbf_potrs": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_chol_append": [P, P, P, P, P, c_int, c_int, P],
     "bcbf_gp_append": [P] * 17 + [c_int, c_int, c_int, c_int, P],

@@ -701,9 +701,7 @@ socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __re
             T n0 = x0, n1 = x1, n2 = th, u0 = T(0), u1 = T(0);
             if (st_code == BCBF_SOCP_OPTIMAL) {  // An instance whose program was not solved keeps its state: the reference raises
                 u0 = (T)x[0]; u1 = (T)x[1];      // there (unicycle_move_to_pose.py:954-964), a batch freezes the instance and
-                n0 = x0 + cos(th) * u0 * task.dt;                 // reports it in status[]
-                n1 = x1 + sin(th) * u0 * task.dt;
-                n2 = th + u1 / task.L_true * task.dt;
+                ackermann_euler<T>(x0, x1, th, u0, u1, task.dt, task.L_true, n0, n1, n2);     // reports it in status[]
                 xs[0] = n0; xs[1] = n1; xs[2] = n2;
             }
             unicycle_observe<T>(task, b, x0, x1, th, n0, n1, n2, u0, u1);
@@ -718,39 +716,18 @@ socp_quad_kernel(const T* __restrict__ w, const T* __restrict__ r, const T* __re
             if (solved) {
                 u0 = (T)x[0]; u1 = (T)x[1];      // y as stored (rounded to T)
                 const double ub[3] = {1.0, (double)u0, (double)u1};
-                double s_ = 0.0;
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) s_ += ub[a] * (double)keep.Bk[a * 3 + c] * ub[c];
-                const double rs = __builtin_sqrt(fmax(s_, 0.0));
-                double LA[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double d = (double)keep.A[j * 3 + j];
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) if (q < j) d -= LA[j][q] * LA[j][q];
-                    if (d > 0.0) {               // (else: the column stays zero)
-                        const double ljj = __builtin_sqrt(d);
-                        LA[j][j] = ljj;
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) if (i > j) {
-                            double v = (double)keep.A[i * 3 + j];
-#pragma unroll
-                            for (int q = 0; q < 3; ++q) if (q < j) v -= LA[i][q] * LA[j][q];
-                            LA[i][j] = v / ljj;
-                        }
-                    }
-                }
-                const double z0 = (double)task.z[(size_t)b * 3], z1 = (double)task.z[(size_t)b * 3 + 1],
-                             z2 = (double)task.z[(size_t)b * 3 + 2];
+                const double rs = __builtin_sqrt(fmax(quad_form3<T>(ub, keep.Bk), 0.0));
+                double LA[3][3];
+                psd_chol3<T>(keep.A, LA);
+                const double z[3] = {(double)task.z[(size_t)b * 3], (double)task.z[(size_t)b * 3 + 1], (double)task.z[(size_t)b * 3 + 2]};
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
                     const double gu = (double)keep.g[d][0] * ub[1] + (double)keep.g[d][1] * ub[2];      // fhat = 0
                     const double mu = (double)keep.Mk[d * 3] + (double)keep.Mk[d * 3 + 1] * ub[1] + (double)keep.Mk[d * 3 + 2] * ub[2];
-                    xd[d] = gu + mu + rs * (LA[d][0] * z0 + LA[d][1] * z1 + LA[d][2] * z2);
+                    xd[d] = posterior_draw(gu + mu, rs, LA[d], z);
                 }
-                cb = keep.sg * ((double)keep.row[0] * xd[0] + (double)keep.row[1] * xd[1] + (double)keep.row[2] * xd[2] + (double)keep.cst);
+                const double row[3] = {(double)keep.row[0], (double)keep.row[1], (double)keep.row[2]};
+                cb = cbc_on(keep.sg, row, xd, (double)keep.cst);
             }
             if (active && task.cbc_s != nullptr) task.cbc_s[(size_t)b * K + k] = (T)cb;
             if (k == 0) {

@@ -14,27 +14,25 @@
 //          block maximum over all of them; wave shuffles, the four waves through LDS, no float atomics.  fp64 in both precisions
 //          (Nte Kob / 256 evaluations per thread against Nte^2 / 512 pairs).
 // Each of the three is rounded to the working type before the closed forms read it, so the results are those of
-// bcbf_trigger_interval fed the same three numbers.  Thread 0 then acts: clamp, Euler step of the true plant (the arithmetic of
-// bcbf_unicycle_step), the instance's clock, its event count and the planner rows of its new time.  An instance whose clock has
-// reached t_end leaves before anything is read or written.
+// bcbf_trigger_interval fed the same three numbers.  Thread 0 then acts: clamp, Euler step of the true plant (ackermann_euler's
+// expressions, unicycle_task.h), the instance's clock, its event count and the planner rows of its new time.  An instance
+// whose clock has reached t_end leaves before anything is read or written.
 //
-// bcbf_unicycle_trigger_step_audit is the same launch with two optional pieces of work for thread 0, in fp64 from the values as the
-// working type stores them, every output rounded once (the second instantiation of trigger_step_body; the plain entry's code is
-// the first and does not change with it):
+// That is one body (trigger_step_body) behind one kernel template and one launcher.  Two optional argument groups add work for
+// thread 0; a group the entry does not take is not compiled in, a pointer the caller leaves null switches its piece off.
+// Group Q, TriggerAuditArgs (bcbf_unicycle_trigger_step_audit, _observe), in fp64 from the values as the working type stores them,
+// every output rounded once, with the draw and the counters of unicycle_task.h that the periodic loop's kernels call:
 //   the plant drawn from the posterior (z given): a solved instance moves by xdot_s = fhat + ghat u + M_k ubar +
-//     sqrt(max(ubar' B_k ubar, 0)) L_A z held for dt_b -- the arithmetic of the sampled branch of socp_quad_kernel, which does
-//     nothing when the solve is called with dt = 0 -- with the risk bookkeeping of rollout_risk_kernel (unicycle.hip), done here
-//     because that kernel cannot tell an idle instance from a live one;
+//     sqrt(max(ubar' B_k ubar, 0)) L_A z held for dt_b (the sampled solve does nothing when called with dt = 0), and the risk
+//     counters are kept here because rollout_risk_kernel cannot tell an idle instance from a live one;
 //   the audit of the held control (u_held given): the two sides of every obstacle row's cone, mean >= rho std, evaluated with
 //     the control of the instance's PREVIOUS event on the rows the solve of this event wrote at the state where that control is
 //     released -- what tau promised, measured one launch later.
-//
-// bcbf_unicycle_trigger_step_observe is that launch with a third optional piece of work for thread 0, after the plant step (the
-// third instantiation of trigger_step_body; the code of the first two does not change with it): the event as the learner's
-// observation row -- unicycle_observe (unicycle_task.h), the function the periodic solve / plant launch calls, on the states as
-// stored and with the event's own hold dt_b in place of the batch's dt -- written to the stream row the instance's OWN event
-// count names, so one captured graph serves every event, and the shift-invariant query of the next solve.  Plain vector stores
-// from one lane, no atomics.
+// Group O, TriggerObserveArgs (bcbf_unicycle_trigger_step_observe), after the plant step: the event as the learner's observation
+// row -- unicycle_observe (unicycle_task.h), the function the periodic solve / plant launch calls, on the states as stored and
+// with the event's own hold dt_b in place of the batch's dt -- written to the stream row the instance's OWN event count names,
+// so one captured graph serves every event, and the shift-invariant query of the next solve.  Plain vector stores from one
+// lane, no atomics.
 #include "trigger_pairs.h"
 #include "unicycle_task.h"
 #include <stdio.h>
@@ -55,8 +53,8 @@ struct TriggerStepArgs {
     int per_instance_hyper, Kob, Nte, P;
 };
 
-// what bcbf_unicycle_trigger_step_audit adds to the arguments: the rows of the solve, the posterior plant (z == nullptr: the true
-// plant) and the audit of the held control (u_held == nullptr: none)
+// group Q: the rows of the solve, the posterior plant (z == nullptr: the true plant) and the audit of the held control
+// (u_held == nullptr: none)
 template <typename T>
 struct TriggerAuditArgs {
     const T* Bk; const T* A; const T* grad; const T* cst; const T* sign; const T* rho;
@@ -65,11 +63,11 @@ struct TriggerAuditArgs {
 };
 struct TriggerNoAudit {};
 
-// what bcbf_unicycle_trigger_step_observe adds to those: the observation stream (obs_x == nullptr: no rows) and the next query
-// (xq_next == nullptr: none)
+// group O: the observation stream (obs_x == nullptr: no rows) and the next query (xq_next == nullptr: none); flags bit 0:
+// shift-invariant inputs
 template <typename T>
 struct TriggerObserveArgs {
-    T L_mean; T* obs_x; T* obs_uh; T* obs_y; int obs_ld, obs_row0, obs_every; T* xq_next; int shift_invariant;
+    T L_mean; T* obs_x; T* obs_uh; T* obs_y; int obs_ld, obs_row0, obs_every; T* xq_next; int flags;
 };
 struct TriggerNoObserve {};
 
@@ -97,32 +95,20 @@ __device__ inline double model_velocity(const TriggerStepArgs<T>& a, int b, int 
     return (double)a.fhat[(size_t)b * 3 + d] + gu + mu;
 }
 
-// c as the counters see it: NaN is below everything (it counts as negative and takes the minimum)
-template <typename T> __device__ inline T nan_is_lowest(T c) { return c == c ? c : T(-INFINITY); }
-
 // The audit of the held control (one thread): mean_k, margin_k = mean_k - rho std_k of the obstacle rows for ubar_h = (1, u_held)
 template <typename T>
 __device__ inline void audit_held_control(const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, int b) {
     const double ub[3] = {1.0, (double)q.u_held[(size_t)b * 2], (double)q.u_held[(size_t)b * 2 + 1]};
-    const T* Bk = q.Bk + (size_t)b * 9;
-    const T* A = q.A + (size_t)b * 9;
-    double s = 0.0, m[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s += ub[i] * (double)Bk[i * 3 + c] * ub[c];
+    const double s = quad_form3<T>(ub, q.Bk + (size_t)b * 9);
+    double m[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) m[d] = model_velocity<T>(a, b, d, ub);
     const double rho = (double)q.rho[b];
     for (int k = 1; k <= a.Kob; ++k) {
         const T* gr = q.grad + ((size_t)b * (1 + a.Kob) + k) * 3;
         const double g[3] = {(double)gr[0], (double)gr[1], (double)gr[2]};
-        double gAg = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) gAg += g[i] * (double)A[i * 3 + c] * g[c];
-        const double mean = (double)q.sign[k] * (g[0] * m[0] + g[1] * m[1] + g[2] * m[2] + (double)q.cst[(size_t)b * (1 + a.Kob) + k]);
+        const double gAg = quad_form3<T>(g, q.A + (size_t)b * 9);
+        const double mean = cbc_on((double)q.sign[k], g, m, (double)q.cst[(size_t)b * (1 + a.Kob) + k]);
         const double margin = mean - rho * sqrt(fmax(s * gAg, 0.0));
         const size_t o = (size_t)b * a.Kob + k - 1;
         const T v[2] = {(T)mean, (T)margin};           // the counters see what is stored
@@ -146,36 +132,13 @@ __device__ inline void posterior_plant_step(const TriggerStepArgs<T>& a, const T
     double xd[3] = {0.0, 0.0, 0.0};
     if (solved) {
         const double ub[3] = {1.0, (double)u0, (double)u1};
-        const T* Bk = q.Bk + (size_t)b * 9;
-        const T* A = q.A + (size_t)b * 9;
-        double s_ = 0.0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s_ += ub[i] * (double)Bk[i * 3 + c] * ub[c];
-        const double rs = __builtin_sqrt(fmax(s_, 0.0));
-        double LA[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double d = (double)A[j * 3 + j];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) if (p < j) d -= LA[j][p] * LA[j][p];
-            if (d > 0.0) {                           // (else: the column stays zero)
-                const double ljj = __builtin_sqrt(d);
-                LA[j][j] = ljj;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) if (i > j) {
-                    double v = (double)A[i * 3 + j];
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) if (p < j) v -= LA[i][p] * LA[j][p];
-                    LA[i][j] = v / ljj;
-                }
-            }
-        }
-        const double z0 = (double)q.z[(size_t)b * 3], z1 = (double)q.z[(size_t)b * 3 + 1], z2 = (double)q.z[(size_t)b * 3 + 2];
+        const double rs = __builtin_sqrt(fmax(quad_form3<T>(ub, q.Bk + (size_t)b * 9), 0.0));
+        double LA[3][3];
+        psd_chol3<T>(q.A + (size_t)b * 9, LA);
+        const double z[3] = {(double)q.z[(size_t)b * 3], (double)q.z[(size_t)b * 3 + 1], (double)q.z[(size_t)b * 3 + 2]};
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            xd[d] = model_velocity<T>(a, b, d, ub) + rs * (LA[d][0] * z0 + LA[d][1] * z1 + LA[d][2] * z2);
+            xd[d] = posterior_draw(model_velocity<T>(a, b, d, ub), rs, LA[d], z);
             a.x[(size_t)b * 3 + d] = (T)((double)xb[d] + xd[d] * (double)dt);
         }
         if (q.solved) q.solved[b] += 1;
@@ -188,15 +151,11 @@ __device__ inline void posterior_plant_step(const TriggerStepArgs<T>& a, const T
         T cb = T(0);
         if (solved) {
             const T* gr = q.grad + ((size_t)b * K + k) * 3;
-            cb = (T)((double)q.sign[k] * ((double)gr[0] * xd[0] + (double)gr[1] * xd[1] + (double)gr[2] * xd[2] + (double)q.cst[(size_t)b * K + k]));
+            const double g[3] = {(double)gr[0], (double)gr[1], (double)gr[2]};
+            cb = (T)cbc_on((double)q.sign[k], g, xd, (double)q.cst[(size_t)b * K + k]);
         }
         if (q.cbc_s) q.cbc_s[(size_t)b * K + k] = cb;
-        if (solved && k > 0 && q.solved) {           // rollout_risk_kernel's bookkeeping: a non-finite value is a violation
-            const size_t o = (size_t)b * a.Kob + k - 1;
-            const T c = cb - cb == T(0) ? cb : T(-INFINITY), mn = q.min_cbc[o];
-            q.viol[o] += c < T(0) ? 1 : 0;
-            q.min_cbc[o] = c < mn ? c : mn;
-        }
+        if (solved && k > 0 && q.solved) risk_count<T>(cb, q.viol + (size_t)b * a.Kob + k - 1, q.min_cbc + (size_t)b * a.Kob + k - 1);
     }
 }
 
@@ -208,7 +167,7 @@ __device__ inline void observe_event(const TriggerStepArgs<T>& a, const TriggerO
     UnicycleTask<T> task = {};
     task.L_mean = o.L_mean;
     task.dt = dt;
-    task.shift_invariant = o.shift_invariant;
+    task.shift_invariant = o.flags & 1;
     task.advance_plan = 0;
     task.xq_next = o.xq_next;
     const int e = a.events[b];
@@ -226,10 +185,10 @@ __device__ inline void observe_event(const TriggerStepArgs<T>& a, const TriggerO
     unicycle_observe<T>(task, b, xb[0], xb[1], xb[2], n0, n1, n2, solved ? u0 : T(0), solved ? u1 : T(0));
 }
 
-// The event of one instance by its workgroup.  AUDIT = false, Q = TriggerNoAudit: bcbf_unicycle_trigger_step; O = TriggerNoObserve:
-// that entry and bcbf_unicycle_trigger_step_audit.
-template <typename T, bool AUDIT, typename Q, typename O = TriggerNoObserve>
-__device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, const Q& au, const O& ob = O{}) {
+// The event of one instance by its workgroup.  Q = TriggerNoAudit: bcbf_unicycle_trigger_step; O = TriggerNoObserve: that entry
+// and bcbf_unicycle_trigger_step_audit.
+template <typename T, typename Q = TriggerNoAudit, typename O = TriggerNoObserve>
+__device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, const Q& au = Q{}, const O& ob = O{}) {
     constexpr int NS = 3, ST = ti_stride(NS);
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_raw[];
     __shared__ T ts_red[TI_WAVES][NS];
@@ -273,7 +232,9 @@ __device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, c
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    // ubar' Bhyp ubar and the model's predicted velocity, then the closed forms on the three numbers as the working type holds them
+    // ubar' Bhyp ubar and the model's predicted velocity, then the closed forms on the three numbers as the working type holds them.
+    // (This quadratic form and the Euler step below stay written out: called through quad_form3 / ackermann_euler the compiler
+    // schedules the plain entry's kernel differently, and that kernel's code is held fixed.)
     const T u0 = a.y[(size_t)b * 3], u1 = a.y[(size_t)b * 3 + 1];
     const double ub[3] = {1.0, (double)u0, (double)u1};
     double uB = 0.0, v2 = 0.0;
@@ -283,11 +244,7 @@ __device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, c
         for (int c = 0; c < 3; ++c) uB += ub[i] * (double)a.Bhyp[(size_t)hb * 9 + i * 3 + c] * ub[c];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const T* g = a.ghat + ((size_t)b * 3 + d) * 2;
-        const T* M = a.Mk + ((size_t)b * 3 + d) * 3;
-        const double gu = (double)g[0] * ub[1] + (double)g[1] * ub[2];
-        const double mu = (double)M[0] + (double)M[1] * ub[1] + (double)M[2] * ub[2];
-        const double v = (double)a.fhat[(size_t)b * 3 + d] + gu + mu;
+        const double v = model_velocity<T>(a, b, d, ub);
         v2 += v * v;
     }
     const T uBT = (T)uB, xvT = (T)sqrt(v2), lhT = (T)lh;
@@ -312,7 +269,7 @@ __device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, c
     const bool last = !(hold < left);
     const T dtT = (T)(last ? left : hold);
     bool euler = solved;
-    if constexpr (AUDIT) {
+    if constexpr (!std::is_same<Q, TriggerNoAudit>::value) {
         // what the last control does at the state where it is released, on this event's rows, before anything of the event
         if (au.u_held != nullptr && au.held[b] != 0) audit_held_control<T>(a, au, b);
         if (au.z != nullptr) {                         // ... the plant drawn from the posterior over it
@@ -346,24 +303,15 @@ __device__ __forceinline__ void trigger_step_body(const TriggerStepArgs<T>& a, c
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const TriggerStepArgs<T> a) {
-    trigger_step_body<T, false>(a, TriggerNoAudit{});
+// G: nothing, (TriggerAuditArgs<T>) or (TriggerAuditArgs<T>, TriggerObserveArgs<T>)
+template <typename T, typename... G>
+__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_kernel(const TriggerStepArgs<T> a, const G... g) {
+    trigger_step_body<T>(a, g...);
 }
 
+// the argument checks, one overload per group present, each after the ones before it
 template <typename T>
-__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_audit_kernel(const TriggerStepArgs<T> a, const TriggerAuditArgs<T> q) {
-    trigger_step_body<T, true>(a, q);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(TI_THREADS) unicycle_trigger_step_observe_kernel(const TriggerStepArgs<T> a, const TriggerAuditArgs<T> q,
-                                                                                   const TriggerObserveArgs<T> o) {
-    trigger_step_body<T, true>(a, q, o);
-}
-
-template <typename T>
-static int trigger_step_args_ok(const char* entry, const TriggerStepArgs<T>& a, int Bt, int Bh) {
+static int trigger_args_ok(const char* entry, const TriggerStepArgs<T>& a, int Bt, int Bh) {
     static thread_local char msg[280];
     const char* why = nullptr;
     if (!a.x || !a.y || !a.status || !a.fhat || !a.ghat || !a.Mk) why = "null control-step buffer (x, y, status, fhat, ghat, Mk)";
@@ -389,19 +337,8 @@ static int trigger_step_args_ok(const char* entry, const TriggerStepArgs<T>& a, 
 }
 
 template <typename T>
-static int launch_trigger_step(const char* entry, TriggerStepArgs<T> a, int Bt, int Bh, void* stream) {
-    if (!trigger_step_args_ok<T>(entry, a, Bt, Bh)) return BCBF_EINVAL;
-    a.per_instance_hyper = Bh == Bt && Bt > 1 ? 1 : 0;
-    const size_t lds = (size_t)a.Nte * ti_stride(3) * sizeof(T);
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((unicycle_trigger_step_kernel<T>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a);
-    return check_launch(entry);
-}
-
-template <typename T>
-static int trigger_audit_args_ok(const char* entry, const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, int Bt, int Bh) {
-    if (!trigger_step_args_ok<T>(entry, a, Bt, Bh)) return 0;
+static int trigger_args_ok(const char* entry, const TriggerStepArgs<T>& a, int Bt, int Bh, const TriggerAuditArgs<T>& q) {
+    if (!trigger_args_ok<T>(entry, a, Bt, Bh)) return 0;
     static thread_local char msg[280];
     const int counters = (q.viol != nullptr) + (q.solved != nullptr) + (q.min_cbc != nullptr);
     const int held = (q.u_held != nullptr) + (q.held != nullptr) + (q.held_mean != nullptr) + (q.held_margin != nullptr) +
@@ -420,20 +357,9 @@ static int trigger_audit_args_ok(const char* entry, const TriggerStepArgs<T>& a,
 }
 
 template <typename T>
-static int launch_trigger_step_audit(const char* entry, TriggerStepArgs<T> a, const TriggerAuditArgs<T>& q, int Bt, int Bh, void* stream) {
-    if (!trigger_audit_args_ok<T>(entry, a, q, Bt, Bh)) return BCBF_EINVAL;
-    a.per_instance_hyper = Bh == Bt && Bt > 1 ? 1 : 0;
-    const size_t lds = (size_t)a.Nte * ti_stride(3) * sizeof(T);
-    if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_audit_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((unicycle_trigger_step_audit_kernel<T>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a, q);
-    return check_launch(entry);
-}
-
-template <typename T>
-static int trigger_observe_args_ok(const char* entry, const TriggerStepArgs<T>& a, const TriggerAuditArgs<T>& q, const TriggerObserveArgs<T>& o,
-                                   int flags, int Bt, int Bh) {
-    if (!trigger_audit_args_ok<T>(entry, a, q, Bt, Bh)) return 0;
+static int trigger_args_ok(const char* entry, const TriggerStepArgs<T>& a, int Bt, int Bh, const TriggerAuditArgs<T>& q,
+                           const TriggerObserveArgs<T>& o) {
+    if (!trigger_args_ok<T>(entry, a, Bt, Bh, q)) return 0;
     static thread_local char msg[280];
     const int rows = (o.obs_x != nullptr) + (o.obs_uh != nullptr) + (o.obs_y != nullptr);
     const char* why = nullptr;
@@ -442,80 +368,63 @@ static int trigger_observe_args_ok(const char* entry, const TriggerStepArgs<T>& 
     else if (rows && o.obs_row0 < 0) why = "obs_row0 < 0";
     else if (rows && o.obs_every < 1) why = "obs_every < 1";
     else if (rows && (o.L_mean != o.L_mean || o.L_mean == T(0))) why = "L_mean must be a number other than 0 (the rows subtract g(theta; L_mean) u)";
-    else if (flags & ~1) why = "flags: only bit 0 (shift-invariant inputs) is defined";
+    else if (o.flags & ~1) why = "flags: only bit 0 (shift-invariant inputs) is defined";
     if (!why) return 1;
     snprintf(msg, sizeof(msg), "%s: %s (Bt=%d rows=%d/3 obs_ld=%d obs_row0=%d obs_every=%d L_mean=%g flags=%d)", entry, why, Bt, rows,
-             o.obs_ld, o.obs_row0, o.obs_every, (double)o.L_mean, flags);
+             o.obs_ld, o.obs_row0, o.obs_every, (double)o.L_mean, o.flags);
     set_error_message(msg);
     return 0;
 }
 
-template <typename T>
-static int launch_trigger_step_observe(const char* entry, TriggerStepArgs<T> a, const TriggerAuditArgs<T>& q, const TriggerObserveArgs<T>& o,
-                                       int flags, int Bt, int Bh, void* stream) {
-    if (!trigger_observe_args_ok<T>(entry, a, q, o, flags, Bt, Bh)) return BCBF_EINVAL;
+// the one launcher: the checks of the groups present, then unicycle_trigger_step_kernel<T, G...>
+template <typename T, typename... G>
+static int launch_trigger_step(const char* entry, TriggerStepArgs<T> a, int Bt, int Bh, void* stream, const G&... g) {
+    if (!trigger_args_ok<T>(entry, a, Bt, Bh, g...)) return BCBF_EINVAL;
     a.per_instance_hyper = Bh == Bt && Bt > 1 ? 1 : 0;
     const size_t lds = (size_t)a.Nte * ti_stride(3) * sizeof(T);
     if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_observe_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((unicycle_trigger_step_observe_kernel<T>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a, q, o);
+        (void)hipFuncSetAttribute((const void*)unicycle_trigger_step_kernel<T, G...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((unicycle_trigger_step_kernel<T, G...>), dim3(Bt), dim3(TI_THREADS), lds, (hipStream_t)stream, a, g...);
     return check_launch(entry);
 }
 
 }  // namespace bcbf
 
+// the parameters the three entries share, in ABI order (include/bcbf.h), and the argument groups they fill
+#define BCBF_TS_PARAMS(T)                                                                                                         \
+    T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off,  \
+        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha,            \
+        double tau_min, double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, \
+        int* events, T* plan, T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu
+#define BCBF_TS_ARGS(T)                                                                                                           \
+    bcbf::TriggerStepArgs<T> {                                                                                                    \
+        x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, tau_min, tau_max, t_end,   \
+            L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P \
+    }
+#define BCBF_TS_AUDIT_PARAMS(T)                                                                                                   \
+    const T* Bk, const T* A, const T* grad, const T* cst, const T* sign, const T* rho, const T* z, T* xdot_s, T* cbc_s, int* viol, \
+        int* solved, T* min_cbc, T* u_held, int* held, T* held_mean, T* held_margin, int* audit_n, int* audit_neg, T* audit_min
+#define BCBF_TS_AUDIT_ARGS(T)                                                                                                     \
+    bcbf::TriggerAuditArgs<T> {                                                                                                   \
+        Bk, A, grad, cst, sign, rho, z, xdot_s, cbc_s, viol, solved, min_cbc, u_held, held, held_mean, held_margin, audit_n,      \
+            audit_neg, audit_min                                                                                                  \
+    }
+#define BCBF_TS_SIZES int Bt, int Bh, int Kob, int Nte, int P, void* stream
 #define BCBF_TRIGGER_STEP(T, SUF)                                                                                                 \
-    extern "C" int bcbf_unicycle_trigger_step_##SUF(                                                                              \
-        T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off, \
-        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, \
-        double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, int* events, T* plan, \
-        T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu, int Bt, int Bh, int Kob, int Nte, int P, void* stream) { \
-        bcbf::TriggerStepArgs<T> a = {x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, \
-                                      tau_min, tau_max, t_end, L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, \
-                                      dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P};                                          \
-        return bcbf::launch_trigger_step<T>("bcbf_unicycle_trigger_step_" #SUF, a, Bt, Bh, stream);                               \
+    extern "C" int bcbf_unicycle_trigger_step_##SUF(BCBF_TS_PARAMS(T), BCBF_TS_SIZES) {                                           \
+        return bcbf::launch_trigger_step<T>("bcbf_unicycle_trigger_step_" #SUF, BCBF_TS_ARGS(T), Bt, Bh, stream);                 \
+    }                                                                                                                             \
+    extern "C" int bcbf_unicycle_trigger_step_audit_##SUF(BCBF_TS_PARAMS(T), BCBF_TS_AUDIT_PARAMS(T), BCBF_TS_SIZES) {            \
+        return bcbf::launch_trigger_step<T>("bcbf_unicycle_trigger_step_audit_" #SUF, BCBF_TS_ARGS(T), Bt, Bh, stream,            \
+                                            BCBF_TS_AUDIT_ARGS(T));                                                               \
+    }                                                                                                                             \
+    extern "C" int bcbf_unicycle_trigger_step_observe_##SUF(BCBF_TS_PARAMS(T), BCBF_TS_AUDIT_PARAMS(T), float L_mean, T* obs_x,   \
+                                                            T* obs_uh, T* obs_y, int obs_ld, int obs_row0, int obs_every,         \
+                                                            T* xq_next, int flags, BCBF_TS_SIZES) {                               \
+        return bcbf::launch_trigger_step<T>(                                                                                      \
+            "bcbf_unicycle_trigger_step_observe_" #SUF, BCBF_TS_ARGS(T), Bt, Bh, stream, BCBF_TS_AUDIT_ARGS(T),                   \
+            bcbf::TriggerObserveArgs<T>{(T)L_mean, obs_x, obs_uh, obs_y, obs_ld, obs_row0, obs_every, xq_next, flags});           \
     }
 BCBF_TRIGGER_STEP(float, f32)
 BCBF_TRIGGER_STEP(double, f64)
-#undef BCBF_TRIGGER_STEP
 
-#define BCBF_TRIGGER_STEP_AUDIT(T, SUF)                                                                                           \
-    extern "C" int bcbf_unicycle_trigger_step_audit_##SUF(                                                                        \
-        T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off, \
-        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, \
-        double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, int* events, T* plan, \
-        T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu, const T* Bk, const T* A, const T* grad, const T* cst, \
-        const T* sign, const T* rho, const T* z, T* xdot_s, T* cbc_s, int* viol, int* solved, T* min_cbc, T* u_held, int* held,   \
-        T* held_mean, T* held_margin, int* audit_n, int* audit_neg, T* audit_min, int Bt, int Bh, int Kob, int Nte, int P,         \
-        void* stream) {                                                                                                           \
-        bcbf::TriggerStepArgs<T> a = {x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, \
-                                      tau_min, tau_max, t_end, L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, \
-                                      dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P};                                          \
-        const bcbf::TriggerAuditArgs<T> q = {Bk, A, grad, cst, sign, rho, z, xdot_s, cbc_s, viol, solved, min_cbc, u_held, held,  \
-                                             held_mean, held_margin, audit_n, audit_neg, audit_min};                              \
-        return bcbf::launch_trigger_step_audit<T>("bcbf_unicycle_trigger_step_audit_" #SUF, a, q, Bt, Bh, stream);                \
-    }
-BCBF_TRIGGER_STEP_AUDIT(float, f32)
-BCBF_TRIGGER_STEP_AUDIT(double, f64)
-#undef BCBF_TRIGGER_STEP_AUDIT
-
-#define BCBF_TRIGGER_STEP_OBSERVE(T, SUF)                                                                                         \
-    extern "C" int bcbf_unicycle_trigger_step_observe_##SUF(                                                                      \
-        T* x, const T* y, const int* status, const T* fhat, const T* ghat, const T* Mk, const T* centers, const T* tw, const T* off, \
-        double r, const T* ls, const T* sf, const T* Adiag, const T* Bhyp, double deltaL, double zeta, double L_alpha, double tau_min, \
-        double tau_max, double t_end, T L_true, const T* plan_all, const T* dplan_all, double dt_plan, double* t, int* events, T* plan, \
-        T* dot_plan, T* tau, T* dt_used, T* Lfh, T* Lkd, T* Lh, T* xvel, T* uBu, const T* Bk, const T* A, const T* grad, const T* cst, \
-        const T* sign, const T* rho, const T* z, T* xdot_s, T* cbc_s, int* viol, int* solved, T* min_cbc, T* u_held, int* held,   \
-        T* held_mean, T* held_margin, int* audit_n, int* audit_neg, T* audit_min, float L_mean, T* obs_x, T* obs_uh, T* obs_y,     \
-        int obs_ld, int obs_row0, int obs_every, T* xq_next, int flags, int Bt, int Bh, int Kob, int Nte, int P, void* stream) {   \
-        bcbf::TriggerStepArgs<T> a = {x, y, status, fhat, ghat, Mk, centers, tw, off, ls, sf, Adiag, Bhyp, r, deltaL, zeta, L_alpha, \
-                                      tau_min, tau_max, t_end, L_true, plan_all, dplan_all, dt_plan, t, events, plan, dot_plan, tau, \
-                                      dt_used, Lfh, Lkd, Lh, xvel, uBu, 0, Kob, Nte, P};                                          \
-        const bcbf::TriggerAuditArgs<T> q = {Bk, A, grad, cst, sign, rho, z, xdot_s, cbc_s, viol, solved, min_cbc, u_held, held,  \
-                                             held_mean, held_margin, audit_n, audit_neg, audit_min};                              \
-        const bcbf::TriggerObserveArgs<T> o = {(T)L_mean, obs_x, obs_uh, obs_y, obs_ld, obs_row0, obs_every, xq_next, flags & 1}; \
-        return bcbf::launch_trigger_step_observe<T>("bcbf_unicycle_trigger_step_observe_" #SUF, a, q, o, flags, Bt, Bh, stream);   \
-    }
-BCBF_TRIGGER_STEP_OBSERVE(float, f32)
-BCBF_TRIGGER_STEP_OBSERVE(double, f64)
-#undef BCBF_TRIGGER_STEP_OBSERVE

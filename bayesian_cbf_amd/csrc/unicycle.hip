@@ -35,11 +35,7 @@ template <typename T>
 __global__ void unicycle_step_kernel(T* __restrict__ x, const T* __restrict__ u, T dt, T L_true, int Bt) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= Bt) return;
-    const T th = x[b * 3 + 2];
-    const T u0 = u[b * 2], u1 = u[b * 2 + 1];
-    x[b * 3] += cos(th) * u0 * dt;
-    x[b * 3 + 1] += sin(th) * u0 * dt;
-    x[b * 3 + 2] += u1 / L_true * dt;
+    ackermann_euler<T>(x[b * 3], x[b * 3 + 1], x[b * 3 + 2], u[b * 2], u[b * 2 + 1], dt, L_true, x[b * 3], x[b * 3 + 1], x[b * 3 + 2]);
 }
 
 // Safety bookkeeping of one closed-loop step of a Monte-Carlo rollout (rollouts.monte_carlo_safety_rollouts), one launch
@@ -78,13 +74,8 @@ __global__ void rollout_risk_kernel(const T* __restrict__ cbc_s, const int* __re
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= Bt || status[b] != 0) return;
     solved[b] += 1;
-    for (int k = 0; k < Kob; ++k) {
-        T c = cbc_s[(size_t)b * (1 + Kob) + 1 + k];
-        if (!(c - c == T(0))) c = -INFINITY;                  // NaN or +-inf
-        viol[(size_t)b * Kob + k] += c < T(0) ? 1 : 0;
-        const T m = min_cbc[(size_t)b * Kob + k];
-        min_cbc[(size_t)b * Kob + k] = c < m ? c : m;
-    }
+    for (int k = 0; k < Kob; ++k)
+        risk_count<T>(cbc_s[(size_t)b * (1 + Kob) + 1 + k], viol + (size_t)b * Kob + k, min_cbc + (size_t)b * Kob + k);
 }
 
 }  // namespace bcbf

@@ -95,6 +95,66 @@ template <typename T> __device__ inline void ackermann_g(T th, T L, T (&G)[3][2]
     G[2][0] = T(0);    G[2][1] = T(1) / L;
 }
 
+// explicit-Euler step of the true Ackermann drive (unicycle_move_to_pose.py:277-282): (x0, x1, th) held at u for dt
+template <typename T> __device__ inline void ackermann_euler(T x0, T x1, T th, T u0, T u1, T dt, T L, T& n0, T& n1, T& n2) {
+    n0 = x0 + cos(th) * u0 * dt;
+    n1 = x1 + sin(th) * u0 * dt;
+    n2 = th + u1 / L * dt;
+}
+
+// The plant drawn from the model's posterior, xdot | x, u ~ N(mean, (ubar' B_k ubar) A) (see UnicycleTask::z), in fp64 from the
+// values as T stores them.  v' M v of a row-major 3x3:
+template <typename T> __device__ inline double quad_form3(const double (&v)[3], const T* M) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s += v[i] * (double)M[i * 3 + c] * v[c];
+    return s;
+}
+
+// A = L_A L_A' of a positive-semidefinite 3x3: a pivot <= 0 leaves its column zero, so the draw stays in the range of A
+template <typename T> __device__ inline void psd_chol3(const T* A, double (&LA)[3][3]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) LA[i][j] = 0.0;
+        double d = (double)A[j * 3 + j];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) if (p < j) d -= LA[j][p] * LA[j][p];
+        if (d > 0.0) {
+            const double ljj = __builtin_sqrt(d);
+            LA[j][j] = ljj;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) if (i > j) {
+                double v = (double)A[i * 3 + j];
+#pragma unroll
+                for (int p = 0; p < 3; ++p) if (p < j) v -= LA[i][p] * LA[j][p];
+                LA[i][j] = v / ljj;
+            }
+        }
+    }
+}
+
+// component d of the draw xd = m + rs L_A z, rs = sqrt(max(ubar' B_k ubar, 0)): m the caller's mean_d, LAd row d of L_A
+__device__ inline double posterior_draw(double m, double rs, const double (&LAd)[3], const double (&z)[3]) {
+    return m + rs * (LAd[0] * z[0] + LAd[1] * z[1] + LAd[2] * z[2]);
+}
+
+// the condition of row k on a state derivative xd: sign_k (grad_k . xd + cst_k) (cbc1.py:10-14)
+__device__ inline double cbc_on(double sign, const double (&g)[3], const double (&xd)[3], double cst) {
+    return sign * (g[0] * xd[0] + g[1] * xd[1] + g[2] * xd[2] + cst);
+}
+
+// The risk counters of one obstacle row see cb: anything non-finite (NaN, +-inf) is a violation and takes the minimum.
+template <typename T> __device__ inline void risk_count(T cb, int* viol, T* min_cbc) {
+    const T c = cb - cb == T(0) ? cb : T(-INFINITY), mn = *min_cbc;
+    *viol += c < T(0) ? 1 : 0;
+    *min_cbc = c < mn ? c : mn;
+}
+// The audit's counters let +-inf through as itself: only NaN is below everything.
+template <typename T> __device__ inline T nan_is_lowest(T c) { return c == c ? c : T(-INFINITY); }
+
 // Everything the fused per-step kernel needs to form the rows itself and to advance the plant afterwards.
 template <typename T>
 struct UnicycleTask {

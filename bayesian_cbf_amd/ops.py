@@ -1445,6 +1445,12 @@ def trigger_observe_workspace(Bt, rows, dtype, device):
                 xq_next=torch.zeros(Bt, 3, **f), shift_invariant=True, L_mean=1.0)
 
 
+def _trigger_want(v, dtype, shape, what):
+    """ValueError unless v is a contiguous tensor of this dtype and shape; `what` names it in the message."""
+    if v.dtype != dtype or not v.is_contiguous() or tuple(v.shape) != shape:
+        raise ValueError("trigger step: %s (%s %s) must be a contiguous %s tensor of shape %s" % (what, v.dtype, tuple(v.shape), dtype, shape))
+
+
 _TRIGGER_OBSERVE_KEYS = ("obs", "ld", "row0", "every", "xq_next", "shift_invariant", "L_mean")
 
 
@@ -1466,12 +1472,9 @@ def _trigger_observe_check(x, observe):
         if not (L_mean != 0.0 and L_mean == L_mean):
             raise ValueError("trigger step: observe['L_mean'] must be a number other than 0")
         for name, v in zip(("obs_x", "obs_uh", "obs_y"), obs):
-            if v.dtype != x.dtype or not v.is_contiguous() or tuple(v.shape) != (Bt, ld, 3):
-                raise ValueError("trigger step: observe['obs'] %s (%s %s) must be a contiguous %s tensor of shape %s"
-                                 % (name, v.dtype, tuple(v.shape), x.dtype, (Bt, ld, 3)))
-    if xq_next is not None and (xq_next.dtype != x.dtype or not xq_next.is_contiguous() or tuple(xq_next.shape) != (Bt, 3)):
-        raise ValueError("trigger step: observe['xq_next'] (%s %s) must be a contiguous %s tensor of shape %s"
-                         % (xq_next.dtype, tuple(xq_next.shape), x.dtype, (Bt, 3)))
+            _trigger_want(v, x.dtype, (Bt, ld, 3), "observe['obs'] %s" % name)
+    if xq_next is not None:
+        _trigger_want(xq_next, x.dtype, (Bt, 3), "observe['xq_next']")
     tensors = (list(obs) if obs is not None else [None] * 3) + [xq_next]
     return tensors, (L_mean, ld, row0, every, 1 if observe.get("shift_invariant", True) else 0)
 
@@ -1509,10 +1512,7 @@ def _trigger_audit_check(task, ws, x, gp_A, sampled, audit):
                 if k in required:
                     raise ValueError("trigger step: %s[%r] is required" % (name, k))
             else:
-                want = torch.int32 if k in ints else x.dtype
-                if v.dtype != want or not v.is_contiguous() or tuple(v.shape) != shapes[k]:
-                    raise ValueError("trigger step: %s[%r] (%s %s) must be a contiguous %s tensor of shape %s"
-                                     % (name, k, v.dtype, tuple(v.shape), want, shapes[k]))
+                _trigger_want(v, torch.int32 if k in ints else x.dtype, shapes[k], "%s[%r]" % (name, k))
             out.append(v)
         return out
 

@@ -503,3 +503,61 @@ def test_defaults_are_the_loop_of_the_old_binding():
     for run in (dflt, expl):
         assert bits(run["x_final"]) == bits(x) and bits(run["t"]) == bits(tws["t"]) and bits(run["events"]) == bits(tws["events"])
         assert "risk" not in run and "audit" not in run
+
+
+# ------------------------------------------------------------------------------------------------ 7. the shared definitions
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+def test_risk_counters_are_those_of_rollout_risk(dtype):
+    """The trigger step's risk counters and bcbf_rollout_risk call one rule.  A launch with draws and fresh counters on a batch with
+    one instance made unsolved, one already at t_end and one with a NaN in an obstacle row's cst; then `ops.rollout_risk` on that
+    launch's cbc_s and status into fresh counters: viol, solved and min_cbc agree bit for bit on the live instances (the NaN row a
+    violation with minimum -inf in both), and the finished instance's counters are as the workspace made them."""
+    from bayesian_cbf_amd import ops
+    Bt, Nte = 5, 27
+    st = G.solved_state(dtype, Bt)
+    hyper, off = G.hyper_and_points(dtype, Bt, Nte, False, seed=31)
+    ok = np.flatnonzero(raw(st["ws"]["status"]) == 0)
+    assert len(ok) >= 2
+    nan_b = int(ok[0])
+    unsolved_b, done_b = [b for b in range(Bt) if b not in ok[:2]][:2]
+    status, cst = st["ws"]["status"].clone(), st["ws"]["cst"].clone()
+    status[unsolved_b] = 2
+    cst[nan_b, 1] = float("nan")
+    t_end, t0 = 5.0, np.zeros(Bt)
+    t0[done_b] = t_end
+    aws = ops.trigger_audit_workspace(Bt, KOB, dtype, DEV)
+    run = run_event(dict(st, ws=dict(st["ws"], cst=cst)), hyper, off, dtype, entry="new", z=draws(Bt, dtype, 41), aws=aws, groups="P",
+                    status=status, t0=t0, t_end=t_end, tau_min=1e-4, tau_max=0.05)
+    s = aws["sampled"]
+    fresh = ops.trigger_audit_workspace(Bt, KOB, dtype, DEV)["sampled"]
+    ops.rollout_risk(s["cbc_s"], run["ws"]["status"], fresh["viol"], fresh["solved"], fresh["min_cbc"])
+    torch.cuda.synchronize()
+    live = torch.as_tensor([b != done_b for b in range(Bt)], device=DEV)
+    for k in ("viol", "solved", "min_cbc"):
+        assert bits(s[k][live]) == bits(fresh[k][live]), k
+    assert np.isnan(raw(s["cbc_s"])[nan_b, 1]) and raw(s["viol"])[nan_b, 0] == 1 and raw(s["min_cbc"])[nan_b, 0] == -np.inf
+    assert raw(s["solved"])[nan_b] == 1 and raw(s["solved"])[unsolved_b] == 0 and not raw(s["viol"])[unsolved_b].any()
+    assert raw(s["solved"])[done_b] == 0 and not raw(s["viol"])[done_b].any() and (raw(s["min_cbc"])[done_b] == np.inf).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+def test_plant_step_is_that_of_unicycle_step(dtype):
+    """The plain entry's Euler step and bcbf_unicycle_step are one definition.  Nte = 1 and tau_min = tau_max = 0.01: every live
+    solved instance holds the same dt, so `ops.unicycle_step` on a copy of the state with u = y[:, :2] and that dt gives the same x
+    bit for bit on the solved instances; the instance made unsolved keeps its state."""
+    from bayesian_cbf_amd import ops
+    Bt, hold = 5, 0.01
+    st = G.solved_state(dtype, Bt)
+    hyper, off = G.hyper_and_points(dtype, Bt, 1, False, seed=32)
+    ok = np.flatnonzero(raw(st["ws"]["status"]) == 0)
+    assert len(ok) >= 2
+    unsolved_b = int(ok[-1])
+    status = st["ws"]["status"].clone()
+    status[unsolved_b] = 2
+    run = run_event(st, hyper, off, dtype, status=status, tau_min=hold, tau_max=hold)
+    solved = torch.as_tensor(raw(status) == 0, device=DEV)
+    assert (raw(run["tws"]["dt_used"][solved]) == NP[dtype](hold)).all()
+    x2 = ops.unicycle_step(st["x"].clone(), st["ws"]["y"][:, :2].contiguous(), hold, G.L_TRUE)
+    torch.cuda.synchronize()
+    assert int(solved.sum()) >= 1 and bits(run["x"][solved]) == bits(x2[solved]) and bits(run["x"][solved]) != bits(st["x"][solved])
+    assert bits(run["x"][unsolved_b]) == bits(st["x"][unsolved_b])
