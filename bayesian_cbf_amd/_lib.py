@@ -113,6 +113,10 @@ _TSIGS = {
     "bcbf_unicycle_constraints": [P, P, P, P, "T", P, P, P, P, "T", P, P, P, P, c_int, c_int, P],
     "bcbf_unicycle_step": [P, P, "T", "T", c_int, P],
     "bcbf_pendulum_plant_step": [P, P, "T", "T", "T", "T", c_int, P],
+    # ("PT": a HOST pointer to values of the entry's precision -- k_alpha[2])
+    "bcbf_pendulum_clf_cbf_control": [P, P, c_int, "T", "PT", "T", "T", "T", c_int, "T"] + [P] * 6 + [c_int, P],
+    "bcbf_pendulum_clf_cbf_rollout": [P, P, c_int, P, c_int, "T", "PT", "T", "T", "T", c_int, "T", "T"] + [P] * 5
+                                     + [c_int] * 4 + [P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],
     "bcbf_unicycle_control_step": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
     "bcbf_unicycle_control_step_matern52": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
@@ -158,7 +162,7 @@ def _load():
         for suf, ct in (("_f32", c_float), ("_f64", c_double)):
             fn = getattr(lib, base + suf)
             fn.restype = c_int
-            fn.argtypes = [ct if a == "T" else a for a in args]
+            fn.argtypes = [ct if a == "T" else ctypes.POINTER(ct) if a == "PT" else a for a in args]
     return lib
 
 

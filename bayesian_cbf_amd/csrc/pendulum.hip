@@ -16,6 +16,7 @@
 // (EpsilonGreedyController, controllers.py:269-285); the plant kernel writes the step's observation row
 // (MeanAdjustedModel.train, controllers.py:320-378).  The Learn = false instantiations are the plain entry's.
 #include "bcbf_common.h"
+#include "pendulum_plant.h"      // pendulum_euler
 
 namespace bcbf {
 
@@ -41,19 +42,6 @@ struct PendulumLearn {
     int has_mean;                               // the mean model the targets subtract (as PendulumParams)
     T mean_mass, mean_gravity, mean_length;
 };
-
-// x <- x + (f(x) + g(x) u) dt,  theta wrapped to [-pi, pi) as ((theta + pi) % 2 pi) - pi with Python's (floored) modulo
-template <typename T>
-__device__ inline void pendulum_euler(T& th, T& om, T u, T mass, T gravity, T length, T dt) {
-    const T xd0 = om;
-    const T xd1 = -(gravity / length) * sin(th) + T(1) / (mass * length) * u;
-    const T tn = th + xd0 * dt;
-    om = om + xd1 * dt;
-    const T two_pi = T(2) * T(M_PI);
-    T r = fmod(tn + T(M_PI), two_pi);
-    if (r < T(0)) r += two_pi;
-    th = r - T(M_PI);
-}
 
 template <typename T, bool Learn>
 __global__ void __launch_bounds__(256)

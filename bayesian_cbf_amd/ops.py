@@ -1756,3 +1756,94 @@ def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_
 def pendulum_control_step(gp, ws, x, **kw):
     """One control step of the pendulum safety filter for a batch (see `pendulum_control_step_prepare`); returns ws['u']."""
     return pendulum_control_step_prepare(gp, ws, x, **kw)()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The pendulum's CLF-CBF quadratic program on the known model (bcbf_pendulum_clf_cbf_control / _rollout):
+# PendulumCBFCLFDirect, the controller the Bayesian one is measured against.  fp32 and fp64.
+_PENDULUM_CBF_KINDS = {"reldeg2": 0, "radial": 1, 0: 0, 1: 1}
+
+
+def _pendulum_model_rows(model, Bt, like, what):
+    """(tensor, stride) of a pendulum model for the library: a (mass, gravity, length) triple or a tensor[3] is one shared
+    row (stride 0), a tensor[Bt,3] one row per instance (stride 3)."""
+    if not torch.is_tensor(model):
+        model = torch.tensor([float(v) for v in model], dtype=like.dtype, device=like.device)
+    if model.dtype != like.dtype or model.device != like.device or not model.is_contiguous():
+        raise TypeError("%s must be a contiguous %s tensor on %s" % (what, like.dtype, like.device))
+    if tuple(model.shape) == (3,):
+        return model, 0
+    if tuple(model.shape) == (Bt, 3):
+        return model, 3
+    raise ValueError("%s must be (mass, gravity, length), a tensor[3] or a tensor[Bt,3]; got %s" % (what, tuple(model.shape)))
+
+
+def _pendulum_qp_task(x, clf_c, k_alpha, theta_c, delta_c, cbf_gamma, cbf_kind, slack_weight):
+    ct = ctypes.c_float if x.dtype == torch.float32 else ctypes.c_double
+    try:
+        kind = _PENDULUM_CBF_KINDS[cbf_kind]
+    except KeyError:
+        raise ValueError("cbf_kind must be 'reldeg2' (0) or 'radial' (1), got %r" % (cbf_kind,))
+    return [clf_c, (ct * 2)(float(k_alpha[0]), float(k_alpha[1])), theta_c, delta_c, cbf_gamma, kind, slack_weight]
+
+
+def pendulum_clf_cbf_control(x, ctrl_model=(1.0, 10.0, 1.0), clf_c=1.0, k_alpha=(1.0, 3.0), theta_c=math.pi / 4,
+                             delta_c=math.pi / 8, cbf_gamma=1.0, cbf_kind="reldeg2", slack_weight=100.0):
+    """One evaluation of the pendulum's CLF-CBF controller on a known model for a batch of states x[Bt,2]: the rows of
+    EnergyCLF (relaxed, slack weight `slack_weight`) and of RadialCBFRelDegree2 (cbf_kind 'reldeg2') or RadialCBF ('radial'),
+    and the optimum of control_QP_cbf_clf in closed form.  ctrl_model: (mass, gravity, length) or a tensor[Bt,3].
+    Returns dict(A[Bt,2], b[Bt,2], values[Bt,2] = (V, h), u[Bt], rho[Bt], status[Bt]); status 1 = the program is
+    infeasible (u, rho are then NaN: the library leaves them unwritten)."""
+    _chk(x)
+    Bt = x.shape[0]
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("x must be [Bt,2]")
+    cm, cs = _pendulum_model_rows(ctrl_model, Bt, x, "ctrl_model")
+    out = dict(A=torch.empty(Bt, 2, dtype=x.dtype, device=x.device), b=torch.empty(Bt, 2, dtype=x.dtype, device=x.device),
+               values=torch.empty(Bt, 2, dtype=x.dtype, device=x.device),
+               u=torch.full((Bt,), float("nan"), dtype=x.dtype, device=x.device),
+               rho=torch.full((Bt,), float("nan"), dtype=x.dtype, device=x.device),
+               status=torch.zeros(Bt, dtype=torch.int32, device=x.device))
+    task = _pendulum_qp_task(x, clf_c, k_alpha, theta_c, delta_c, cbf_gamma, cbf_kind, slack_weight)
+    check(getattr(lib, "bcbf_pendulum_clf_cbf_control" + _suf(x))(
+        _p(x), _p(cm), cs, *task, _p(out["A"]), _p(out["b"]), _p(out["values"]), _p(out["u"]), _p(out["rho"]),
+        _p(out["status"]), Bt, _stream(x)), "bcbf_pendulum_clf_cbf_control")
+    return out
+
+
+def pendulum_clf_cbf_records(t_offset, numSteps, record_every):
+    """How many of the global steps t_offset .. t_offset + numSteps - 1 are multiples of record_every (0: none recorded)."""
+    if record_every <= 0:
+        return 0
+    first = -(-t_offset // record_every)
+    last = -(-(t_offset + numSteps) // record_every)
+    return last - first
+
+
+def pendulum_clf_cbf_rollout(x, min_h, damage, status, numSteps, dt=0.002, ctrl_model=(1.0, 10.0, 1.0), true_model=None,
+                             clf_c=1.0, k_alpha=(1.0, 3.0), theta_c=math.pi / 4, delta_c=math.pi / 8, cbf_gamma=1.0,
+                             cbf_kind="reldeg2", slack_weight=100.0, traj=None, u_rec=None, record_every=0, t_offset=0):
+    """numSteps steps of the closed loop (controller of `pendulum_clf_cbf_control` on ctrl_model, explicit Euler on the plant
+    true_model -- None: the controller's model) for every instance in ONE launch.  In place: x[Bt,2], min_h[Bt],
+    damage[Bt] (int32), status[Bt] (int32; the 1-based global step t_offset + t + 1 at which an instance's program became
+    infeasible -- it is frozen from there on).  Calls compose bit for bit (the second with t_offset = the steps done).
+    traj[r,Bt,2] / u_rec[r,Bt]: (x_t, u_t) of the global steps that are multiples of record_every, this call's first at
+    row 0; r = pendulum_clf_cbf_records(t_offset, numSteps, record_every).  Returns x."""
+    _chk(x, min_h, damage, status, traj, u_rec)
+    Bt = x.shape[0]
+    if x.ndim != 2 or x.shape[1] != 2 or tuple(min_h.shape) != (Bt,) or min_h.dtype != x.dtype:
+        raise ValueError("x must be [Bt,2] and min_h [Bt] of the same dtype")
+    for name, t in (("damage", damage), ("status", status)):
+        if tuple(t.shape) != (Bt,) or t.dtype != torch.int32:
+            raise ValueError("%s must be an int32 tensor [Bt]" % name)
+    cm, cs = _pendulum_model_rows(ctrl_model, Bt, x, "ctrl_model")
+    tm, ts = (cm, cs) if true_model is None else _pendulum_model_rows(true_model, Bt, x, "true_model")
+    nrec = pendulum_clf_cbf_records(t_offset, numSteps, record_every)
+    for name, t, shape in (("traj", traj, (Bt, 2)), ("u_rec", u_rec, (Bt,))):
+        if t is not None and (t.dtype != x.dtype or tuple(t.shape[1:]) != shape or t.shape[0] < nrec):
+            raise ValueError("%s must be a %s tensor [>= %d, %s]" % (name, x.dtype, nrec, ", ".join(map(str, shape))))
+    task = _pendulum_qp_task(x, clf_c, k_alpha, theta_c, delta_c, cbf_gamma, cbf_kind, slack_weight)
+    check(getattr(lib, "bcbf_pendulum_clf_cbf_rollout" + _suf(x))(
+        _p(x), _p(cm), cs, _p(tm), ts, *task, dt, _p(min_h), _p(damage), _p(status), _p(traj), _p(u_rec), record_every,
+        t_offset, numSteps, Bt, _stream(x)), "bcbf_pendulum_clf_cbf_rollout")
+    return x

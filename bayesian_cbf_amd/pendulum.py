@@ -469,3 +469,168 @@ def pendulum_online_learning_rollouts(Bt=4096, numSteps=250, tau=0.002, theta0=7
     from .rollouts import pendulum_learning_rollouts
     return pendulum_learning_rollouts(Bt, numSteps=numSteps, dt=tau, theta0=theta0, omega0=omega0, fit_iters=fit_iters,
                                       learning=True, **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# The CLF-CBF quadratic program on the KNOWN model: PendulumCBFCLFDirect / run_pendulum_control_cbf_clf
+# (pendulum.py:530-640, 770-906, 1019-1024), the controller the Bayesian one is measured against.  Rows and program are
+# evaluated by the library (bcbf_pendulum_clf_cbf_control / _rollout); `rollouts.pendulum_clf_cbf_rollouts` is the batched form.
+def _clf_cbf_eval(x, model, **task):
+    """ops.pendulum_clf_cbf_control for ONE state x[2] (any device / float dtype; evaluated on the GPU in float64, the
+    precision upstream's program is solved in whatever the torch dtype)."""
+    from . import ops
+    dev = x.device if x.is_cuda else torch.device("cuda")
+    xd = x.detach().reshape(1, 2).to(device=dev, dtype=torch.float64).contiguous()
+    return ops.pendulum_clf_cbf_control(xd, ctrl_model=(model.mass, model.gravity, model.length), **task)
+
+
+class _PendulumAffine:
+    """A(x) u - b(x) <= 0, upstream's NamedAffineFunc protocol: value(x), A(x) [1], b(x) (0-d), __call__(x, u)."""
+    _row = None
+
+    def _task(self):
+        raise NotImplementedError
+
+    def _eval(self, x):
+        return _clf_cbf_eval(x, self.model, **self._task())
+
+    def value(self, x):
+        return self._eval(x)["values"][0, self._row].to(x)
+
+    def A(self, x):
+        return self._eval(x)["A"][0, self._row].reshape(1).to(x)
+
+    def b(self, x):
+        return self._eval(x)["b"][0, self._row].to(x)
+
+    def __call__(self, x, u):
+        return self.A(x) @ u.reshape(1).to(x) - self.b(x)
+
+    def __getattr__(self, name):          # upstream forwards unknown attributes to its model (mass, gravity, f_func ...)
+        if name == "model":
+            raise AttributeError(name)
+        return getattr(self.model, name)
+
+
+class EnergyCLF(_PendulumAffine):
+    """V = l omega^2 / 2 + g (1 - cos theta);  A = grad V . g(x) = omega / m,  b = -grad V . f(x) - c V = -c V  (:530-579).
+    These are the values upstream RETURNS; its hand-written `direct = l omega` agrees with them only when m l = 1, and its
+    own assert trips for another model."""
+    _row = 0
+
+    def __init__(self, model, clf_c=1, name="clf"):
+        self.model, self.clf_c, self.name = model, clf_c, name
+
+    V_clf = _PendulumAffine.value
+
+    def _task(self):
+        return dict(clf_c=float(self.clf_c))
+
+
+class RadialCBF(_PendulumAffine):
+    """h = (cos Delta_c - cos(theta - theta_c)) (omega^2 + 1), relative degree 1  (:582-640):  A = -grad h . g(x),
+    b = grad h . f(x) + gamma h."""
+    _row = 1
+
+    def __init__(self, model, cbf_col_gamma=1, k_alpha=(1., 1.), cbf_col_delta=math.pi / 8, cbf_col_theta=math.pi / 4,
+                 theta_c=math.pi / 4, gamma_col=1, delta_col=math.pi / 8, name="cbf"):
+        self.model, self.cbf_col_gamma, self.k_alpha, self.name = model, cbf_col_gamma, list(k_alpha), name
+        self.cbf_col_delta, self.cbf_col_theta = cbf_col_delta, cbf_col_theta
+
+    h_col = _PendulumAffine.value
+
+    def _task(self):
+        return dict(cbf_kind="radial", cbf_gamma=float(self.cbf_col_gamma), theta_c=float(self.cbf_col_theta),
+                    delta_c=float(self.cbf_col_delta))
+
+
+def _clf_cbf_task(ctrl_aff_constraints, constraint_margin_weights):
+    """(model, task keywords of ops.pendulum_clf_cbf_*) of the one program shape upstream builds: [EnergyCLF, barrier] on one
+    pendulum model, one control, one slack on the first row."""
+    cons = list(ctrl_aff_constraints)
+    if (len(cons) != 2 or len(constraint_margin_weights) != 1 or not isinstance(cons[0], EnergyCLF)
+            or not isinstance(cons[1], (RadialCBFRelDegree2, RadialCBF)) or cons[0].model is not cons[1].model):
+        raise NotImplementedError(
+            "control_QP_cbf_clf is built for upstream's program: [EnergyCLF, RadialCBFRelDegree2 or RadialCBF] on one "
+            "pendulum model with constraint_margin_weights = [w]")
+    clf, cbf = cons
+    task = dict(clf_c=float(clf.clf_c), theta_c=float(cbf.cbf_col_theta), delta_c=float(cbf.cbf_col_delta),
+                slack_weight=float(constraint_margin_weights[0]))
+    if isinstance(cbf, RadialCBF):
+        task.update(cbf_kind="radial", cbf_gamma=float(cbf.cbf_col_gamma))
+    else:
+        task.update(cbf_kind="reldeg2", k_alpha=tuple(float(k) for k in cbf.k_alpha))
+    return clf.model, task
+
+
+def control_QP_cbf_clf(x, ctrl_aff_constraints, constraint_margin_weights=[]):
+    """pendulum.py:800-864: minimise 1/2 (u^2 + w rho^2) s.t. A_clf u - rho <= b_clf, A_cbf u <= b_cbf; returns u[1] in x's
+    dtype.  Upstream iterates with cvxopt; here the unique optimum comes in closed form from the library (parity with
+    cvxopt's iterates is not claimed).  Raises RuntimeError("QP is infeasible ...") as upstream does, NotImplementedError
+    for any other shape than upstream's own (two rows, one control, one slack on the first row)."""
+    model, task = _clf_cbf_task(ctrl_aff_constraints, constraint_margin_weights)
+    out = _clf_cbf_eval(x, model, **task)
+    if int(out["status"][0]) != 0:
+        raise RuntimeError("QP is infeasible\n        minimize 1/2 (u^2 + %g rho^2)\n        s.t.\n        %s [u, rho] <= %s"
+                           % (task["slack_weight"], [[float(out["A"][0, 0]), -1.0], [float(out["A"][0, 1]), 0.0]],
+                              out["b"][0].tolist()))
+    return out["u"].to(device=x.device, dtype=x.dtype)
+
+
+class PendulumCBFCLFDirect:
+    """Upstream's PendulumCBFCLFDirect (:867-906), same signature: EnergyCLF (slack weight 100) and RadialCBFRelDegree2 on
+    the known pendulum (mass, gravity, length).  The plotting arguments are accepted and ignored."""
+    needs_ground_truth = True
+
+    def __init__(self, mass=None, length=None, gravity=None, dt=None, constraint_plotter_class=None,
+                 pendulum_dynamics_class=PendulumDynamicsModel, true_model=None, plotfile=None,
+                 dtype=torch.get_default_dtype(), **ignored):
+        self.dt, self.true_model, self.dtype, self.pendulum_dynamics_class = dt, true_model, dtype, pendulum_dynamics_class
+        self.set_model_params(mass=mass, length=length, gravity=gravity)
+
+    def set_model_params(self, **kwargs):
+        self.model = self.pendulum_dynamics_class(m=1, n=2, **kwargs)
+        self.cbf2 = RadialCBFRelDegree2(self.model, dtype=self.dtype)
+        self.aff_constraints = [EnergyCLF(self.model), self.cbf2]
+
+    def f_func(self, x):
+        return self.model.f_func(torch.as_tensor(x))
+
+    def g_func(self, x):
+        return self.model.g_func(torch.as_tensor(x))
+
+    def control(self, xi, i=None, t=None):
+        return control_QP_cbf_clf(xi, ctrl_aff_constraints=self.aff_constraints, constraint_margin_weights=[100])
+
+
+def run_pendulum_control_cbf_clf(theta0=5 * math.pi / 12, omega0=-0.01, tau=0.002, mass=1, gravity=10, length=1,
+                                 numSteps=15000, controller_class=PendulumCBFCLFDirect,
+                                 pendulum_dynamics_class=PendulumDynamicsModel, plotfile=None, dtype=torch.float64,
+                                 device="cuda"):
+    """run_pendulum_control_cbf_clf (pendulum.py:1019-1024 through run_pendulum_experiment, :299-338): the closed loop of
+    PendulumCBFCLFDirect on the true pendulum from (theta0, omega0), numSteps steps of tau -- ONE instance, every step
+    recorded, all steps in one launch of the library's rollout kernel.  Returns upstream's
+    (damge_perc, time_vec, theta_vec, omega_vec, u_vec), each of length numSteps.
+    dtype: float64 by default.  Upstream's default run is float32 states around a float64 solve (its program goes to cvxopt
+    in float64 whatever the torch dtype); dtype=torch.float32 runs rows, program and plant in float32.
+    Raises RuntimeError("QP is infeasible ...") when a step's program is, as upstream's loop does.  plotfile is ignored."""
+    from . import ops
+    ctrl = controller_class(mass=mass, gravity=gravity, length=length, dt=tau, dtype=dtype,
+                            true_model=pendulum_dynamics_class(m=1, n=2, mass=mass, gravity=gravity, length=length, dtype=dtype))
+    if not isinstance(ctrl, PendulumCBFCLFDirect):
+        raise NotImplementedError("run_pendulum_control_cbf_clf runs PendulumCBFCLFDirect")
+    model, task = _clf_cbf_task(ctrl.aff_constraints, [100])
+    f = dict(dtype=dtype, device=device)
+    x = torch.tensor([[theta0, omega0]], **f)
+    min_h = torch.full((1,), float("inf"), **f)
+    damage = torch.zeros(1, dtype=torch.int32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    traj, us = torch.empty(numSteps, 1, 2, **f), torch.empty(numSteps, 1, **f)
+    ops.pendulum_clf_cbf_rollout(x, min_h, damage, status, numSteps, dt=tau, ctrl_model=(model.mass, model.gravity, model.length),
+                                 true_model=(mass, gravity, length), traj=traj, u_rec=us, record_every=1, **task)
+    if int(status[0]) != 0:
+        raise RuntimeError("QP is infeasible at step %d (state %s)" % (int(status[0]) - 1, x[0].tolist()))
+    theta_vec, omega_vec, u_vec = traj[:, 0, 0], traj[:, 0, 1], us[:, 0]
+    assert torch.all((theta_vec <= math.pi) & (-math.pi <= theta_vec))
+    damge_perc = damage[0].to(dtype) * 100 / numSteps
+    return damge_perc, tau * torch.arange(numSteps, **f), theta_vec, omega_vec, u_vec

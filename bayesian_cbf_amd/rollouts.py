@@ -1713,3 +1713,62 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
         out["final"] = dict(rows=final, hyper={key: v.clone() for key, v in hyper.items()},
                             gp=None if model is None else {key: v.clone() for key, v in model.items()})
     return out
+
+
+def pendulum_clf_cbf_rollouts(Bt, numSteps=15000, dt=0.002, theta0=5 * math.pi / 12, omega0=-0.01, start_noise=0.05,
+                              ctrl_model=(1.0, 10.0, 1.0), true_model=None, record_every=0, dtype=torch.float64, seed=0,
+                              steps_per_launch=None, clf_c=1.0, k_alpha=(1.0, 3.0), cbf_col_theta=math.pi / 4,
+                              cbf_col_delta=math.pi / 8, cbf_gamma=1.0, cbf_kind="reldeg2", slack_weight=100.0, x0=None,
+                              device="cuda"):
+    """Bt closed loops of the pendulum's CLF-CBF quadratic program on a KNOWN model (PendulumCBFCLFDirect; the defaults are
+    run_pendulum_control_cbf_clf's, pendulum.py:1019-1024: theta0 = 5 pi / 12, tau = 0.002, 15 000 steps) from perturbed
+    starts, every step of every loop inside the library's rollout kernel (bcbf_pendulum_clf_cbf_rollout): one launch, or
+    ceil(numSteps / steps_per_launch) launches that compose bit for bit.
+
+    ctrl_model: the (mass, gravity, length) the controller believes.  true_model: the plant -- None (= ctrl_model), a
+    triple, or a tensor[Bt,3] (one plant per instance): a plant that differs from the controller's model is the
+    model-mismatch study.  x0: explicit starts [Bt,2] instead of the perturbed ones.  A trajectory collides when
+    min_h < 0 (NaN-safe: anything not provably >= 0 counts); an instance whose program became infeasible is frozen at that
+    step (`status` = its 1-based step, `fails` = status > 0) and contributes the statistics it had until then.
+    In float32 h at the boundary the nominal run settles on (theta = 3 pi / 8, h ~ 2e-6) is below the rounding of
+    cos Delta_c - cos d: the float32 collision count is noise around that boundary, only the float64 count is meaningful.
+    Returns dict(stats (`reduce_rollout_stats`), x_final[Bt,2], min_h[Bt], fails[Bt], damage[Bt], status[Bt],
+    traj[nrec,Bt,2] and u[nrec,Bt] (record_every > 0: the steps that are multiples of it, before the step), loop_seconds)."""
+    dev = torch.device(device)
+    f = dict(dtype=dtype, device=dev)
+    if x0 is None:
+        gen = torch.Generator(device=dev).manual_seed(seed)
+        x = (torch.tensor([theta0, omega0], **f) + start_noise * torch.randn(Bt, 2, generator=gen, **f)).contiguous()
+    else:
+        x = torch.as_tensor(x0).to(**f).reshape(Bt, 2).clone().contiguous()
+    ctrl = torch.tensor([float(v) for v in ctrl_model], **f)
+    true = ctrl if true_model is None else (true_model.to(**f).contiguous() if torch.is_tensor(true_model)
+                                            else torch.tensor([float(v) for v in true_model], **f))
+    min_h = torch.full((Bt,), float("inf"), **f)
+    damage = torch.zeros(Bt, dtype=torch.int32, device=dev)
+    status = torch.zeros(Bt, dtype=torch.int32, device=dev)
+    nrec = ops.pendulum_clf_cbf_records(0, numSteps, record_every)
+    traj = torch.empty(nrec, Bt, 2, **f) if record_every > 0 else None
+    us = torch.empty(nrec, Bt, **f) if record_every > 0 else None
+    chunk = numSteps if not steps_per_launch else int(steps_per_launch)
+    if chunk < 1 and numSteps > 0:
+        raise ValueError("steps_per_launch must be >= 1")
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter()
+    t = 0
+    while t < numSteps:
+        k = min(chunk, numSteps - t)
+        r0 = ops.pendulum_clf_cbf_records(0, t, record_every)
+        ops.pendulum_clf_cbf_rollout(x, min_h, damage, status, k, dt=dt, ctrl_model=ctrl, true_model=true, clf_c=clf_c,
+                                     k_alpha=k_alpha, theta_c=cbf_col_theta, delta_c=cbf_col_delta, cbf_gamma=cbf_gamma,
+                                     cbf_kind=cbf_kind, slack_weight=slack_weight,
+                                     traj=traj[r0:] if traj is not None else None, u_rec=us[r0:] if us is not None else None,
+                                     record_every=record_every, t_offset=t)
+        t += k
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter() - t_loop
+    collided = ~(min_h >= 0)
+    fails = status > 0
+    stats = reduce_rollout_stats(collided.sum(), min_h.min(), 0.0, fails.sum(), Bt)
+    return dict(stats=stats, x_final=x, min_h=min_h, fails=fails, damage=damage, status=status, traj=traj, u=us,
+                loop_seconds=t_loop)

@@ -1101,6 +1101,64 @@ int bcbf_pendulum_control_step_observe_f64(
     double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
     int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
     int obs_ld, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
+
+/* ---- The pendulum's CLF-CBF quadratic program on the KNOWN model (PendulumCBFCLFDirect, run_pendulum_control_cbf_clf:
+ * pendulum.py:530-640, 770-906, 1019-1024).  Two rows, affine in the control, on the controller's model (m, g, l) at
+ * x = (theta, omega), d = theta - theta_c:
+ *   row 0, EnergyCLF (relaxed by the slack rho):  V = l omega^2 / 2 + g (1 - cos theta),  A = omega / m,  b = -clf_c V
+ *     -- the values the reference RETURNS (grad V . g and -grad V . f - c V); its hand-written `direct = l omega` equals
+ *     them only when m l = 1, and its own assert trips for another model;
+ *   row 1 (hard), cbf_kind 0, RadialCBFRelDegree2:  h = cos delta_c - cos d,  A = -sin d / (m l),
+ *     b = omega^2 cos d - (g/l) sin d sin theta + k_alpha[0] h + k_alpha[1] omega sin d;
+ *   row 1 (hard), cbf_kind 1, RadialCBF:  h = (cos delta_c - cos d)(omega^2 + 1),  A = -2 omega (cos delta_c - cos d) / (m l),
+ *     b = grad h . f + cbf_gamma h,  grad h = [sin d (omega^2 + 1), 2 omega (cos delta_c - cos d)];
+ * and control_QP_cbf_clf with constraint_margin_weights = [slack_weight]:
+ *     minimise 1/2 (u^2 + slack_weight rho^2)   subject to   A0 u - rho <= b0,   A1 u <= b1.
+ * The objective is strictly convex: the unique optimum is computed in closed form over the four active sets (the
+ * reference iterates with cvxopt; parity with its iterates is not claimed).  The program is infeasible exactly when
+ * A1 == 0 and b1 < 0: status 1, nothing divided, u and rho not written (a non-finite row or result is reported the same way).
+ * ctrl_params: the controller's (m, g, l), device, one shared row (ctrl_stride = 0) or one row per instance
+ * (ctrl_stride = 3).  k_alpha[2]: HOST values.
+ *
+ * One control evaluation for Bt states, no step: x[Bt,2] -> A[Bt,2], b[Bt,2], values[Bt,2] = (V, h), u[Bt], rho[Bt],
+ * status[Bt] (int); every output may be NULL.
+ * BCBF_EINVAL with a reason in bcbf_last_error, before any HIP call, for: Bt <= 0, null x / ctrl_params / k_alpha,
+ * slack_weight <= 0, ctrl_stride not 0 / 3, cbf_kind not 0 / 1. */
+int bcbf_pendulum_clf_cbf_control_f32(const float* x, const float* ctrl_params, int ctrl_stride, float clf_c,
+                                      const float* k_alpha, float theta_c, float delta_c, float cbf_gamma, int cbf_kind,
+                                      float slack_weight, float* A, float* b, float* values, float* u, float* rho,
+                                      int* status, int Bt, void* stream);
+int bcbf_pendulum_clf_cbf_control_f64(const double* x, const double* ctrl_params, int ctrl_stride, double clf_c,
+                                      const double* k_alpha, double theta_c, double delta_c, double cbf_gamma, int cbf_kind,
+                                      double slack_weight, double* A, double* b, double* values, double* u, double* rho,
+                                      int* status, int Bt, void* stream);
+
+/* The closed loop: numSteps steps for Bt instances in ONE launch, one lane per instance (64-thread workgroups); state,
+ * parameters and statistics stay in registers for the whole launch.  Per step, in sampling_pendulum's order
+ * (pendulum.py:199-226): rows at x_t on the controller's model; the program; min_h = min(min_h, h(x_t)) (a non-finite h
+ * counts as -inf); damage += (0 < theta_t < pi/4); x_{t+1} = x_t + (f + g u) dt on the PLANT's parameters (true_params,
+ * true_stride: as ctrl_params; a plant that differs from the controller's model is the mismatch study); theta wrapped as
+ * bcbf_pendulum_plant_step does.  An instance whose program cannot be solved at (0-based) step t records
+ * status = t_offset + t + 1 and freezes: its state, min_h and damage keep the values they had before that step (the
+ * reference raises there).  An instance that arrives with status != 0 stays frozen.
+ * In/out, accumulated in place: x[Bt,2], min_h[Bt], damage[Bt] (int), status[Bt] (int) -- two calls of k steps, the
+ * second with t_offset = k, equal one call of 2k steps bit for bit.
+ * Recording (traj and/or u_rec given, record_every > 0): the steps whose global index t_offset + t is a multiple of
+ * record_every write (x_t, u_t) -- before the step; u = 0 for a frozen instance -- to traj[r,Bt,2] and u_rec[r,Bt], r
+ * counting from 0 within THIS launch: the caller offsets the pointers between launches and sizes the buffers for
+ * the number of such steps.
+ * BCBF_EINVAL with a reason, before any HIP call, for: Bt <= 0, numSteps < 0, t_offset < 0, dt <= 0, slack_weight <= 0, a
+ * stride not 0 / 3, cbf_kind not 0 / 1, a null required buffer, recording pointers with record_every <= 0. */
+int bcbf_pendulum_clf_cbf_rollout_f32(float* x, const float* ctrl_params, int ctrl_stride, const float* true_params,
+                                      int true_stride, float clf_c, const float* k_alpha, float theta_c, float delta_c,
+                                      float cbf_gamma, int cbf_kind, float slack_weight, float dt, float* min_h, int* damage,
+                                      int* status, float* traj, float* u_rec, int record_every, int t_offset, int numSteps,
+                                      int Bt, void* stream);
+int bcbf_pendulum_clf_cbf_rollout_f64(double* x, const double* ctrl_params, int ctrl_stride, const double* true_params,
+                                      int true_stride, double clf_c, const double* k_alpha, double theta_c, double delta_c,
+                                      double cbf_gamma, int cbf_kind, double slack_weight, double dt, double* min_h,
+                                      int* damage, int* status, double* traj, double* u_rec, int record_every, int t_offset,
+                                      int numSteps, int Bt, void* stream);
 /* The same control step on a model learned with the opt-in Matern-5/2 data kernel (bcbf_refit_matern52 /
  * bcbf_gp_append_matern52 states): identical arguments; the posterior launch evaluates the Matern kernel (one GP per
  * instance: the streaming kernel; shared_gp: the matrix-core query bcbf_posterior_shared_matern52), the fused task rows /
