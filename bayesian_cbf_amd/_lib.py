@@ -40,6 +40,12 @@ _SIGS = {
                                                + [c_int] * 2 + [c_double] * 4 + [P] * 24
                                                + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
                                                + [c_int] * 3 + [P] * 3),
+    # the observing entry's arguments, then (z, xdot_s, cbc_s, relaxed, viol_relaxed, rho_tol)
+    "bcbf_pendulum_control_step_sampled_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
+                                                       ctypes.POINTER(c_double), c_double, P] + [c_double] * 3
+                                               + [c_int] * 2 + [c_double] * 4 + [P] * 24
+                                               + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
+                                               + [P] * 5 + [c_double] + [c_int] * 3 + [P] * 3),
 }
 # the trigger-step entries: the event's 35 arguments, the 19 of the audit group, the 9 of the observe group, (Bt, Bh, Kob, Nte, P, stream)
 _TS_EVENT = [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11

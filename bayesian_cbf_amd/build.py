@@ -32,7 +32,8 @@ EXTRA_FLAGS = {"posterior_shared.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "refit_wave64.hip": ["-fno-slp-vectorize"],
                "posterior_shared_reg.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "posterior_step.hip": ["-Rpass-analysis=kernel-resource-usage"],
-               "pendulum_qp.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+               "pendulum_qp.hip": ["-Rpass-analysis=kernel-resource-usage"],
+               "pendulum.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 # instantiations of the streaming kernel whose measured figures assume ZERO scratch (a spill in the streaming loop is fatal
 # there: DESIGN.md 3.1 -- 1373 us against 470): the headline (fp32 / fp64 values-only, C = 2..3), the fp32 jets of the pendulum and
 # unicycle shapes, the fp32 fused query + append column.  Demangled-name prefixes; the build fails when one of them reports scratch
@@ -45,7 +46,9 @@ ZERO_SCRATCH_KERNELS = {"posterior_step.hip": [
     "posterior_step_kernel<float, 3, 4, 0, 1, false, 1, false, false>", "posterior_step_kernel<float, 3, 4, 0, 1, true, 0,",
     "posterior_step_kernel<double, 4, 4, 0, 1, false, 0,", "posterior_step_kernel<double, 3, 8, 0, 1, false, 0,"],
     # the in-kernel closed loop keeps state, parameters and statistics in registers for all of its steps
-    "pendulum_qp.hip": ["pendulum_clf_cbf_rollout_kernel<float>", "pendulum_clf_cbf_rollout_kernel<double>"]}
+    "pendulum_qp.hip": ["pendulum_clf_cbf_rollout_kernel<float>", "pendulum_clf_cbf_rollout_kernel<double>"],
+    # the posterior-drawn plant: two Cholesky factors, the draw and the condition live in registers (every index a constant)
+    "pendulum.hip": ["pendulum_sampled_plant_kernel<double>"]}
 # kernels that must not touch scratch memory (posterior_shared_reg: an operand spilled between its explicit LDS read and
 # the explicit wait for it would be stored before it has arrived).  Their device assembly is also linted: no instruction may
 # name the destination of an LDS read that has not been waited for (check_lds_waits.py)

@@ -15,8 +15,12 @@
 // kernel can write the GP prior of a regressor with no data and wraps the greedy u_ref in the epsilon-greedy explorer
 // (EpsilonGreedyController, controllers.py:269-285); the plant kernel writes the step's observation row
 // (MeanAdjustedModel.train, controllers.py:320-378).  The Learn = false instantiations are the plain entry's.
+// The sampled entry (bcbf_pendulum_control_step_sampled_f64) runs the observing entry's launches with a third plant kernel: the
+// jet columns the rel-degree-2 condition reads are drawn from the model's own posterior, the state advances on the draw and the
+// condition is evaluated on it (pendulum_posterior_plant.h) -- the instrument that measures what risk the loop actually holds.
 #include "bcbf_common.h"
-#include "pendulum_plant.h"      // pendulum_euler
+#include "pendulum_plant.h"      // pendulum_euler, pendulum_advance
+#include "pendulum_posterior_plant.h"      // the sampled plant kernel's draw
 
 namespace bcbf {
 
@@ -120,15 +124,14 @@ __global__ void __launch_bounds__(256) pendulum_pack_terms_kernel(const T* __res
     for (int i = 0; i < 5; ++i) t[(size_t)b * 5 + i] = t2[(size_t)b * 7 + i];
 }
 
-template <typename T, bool Learn>
-__global__ void __launch_bounds__(256)
-pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int* __restrict__ sstatus,
-                      const int* __restrict__ cstatus, const int* __restrict__ tstatus, const T* __restrict__ u_ref,
-                      const T* __restrict__ h, T* __restrict__ u, int* __restrict__ status, T* __restrict__ min_h,
-                      int* __restrict__ fails, T mass, T gravity, T length, T dt, PendulumLearn<T> L, int Bt) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= Bt) return;
-    const int st = tstatus[b] == 1 ? BCBF_PENDULUM_BADHESSIAN : cstatus[b] != 0 ? BCBF_SOCP_BADCONE : sstatus[b];
+// What both plant kernels do first: status, the applied control u = y[2] where the program was solved and u_ref elsewhere, and the
+// safety bookkeeping on h(x_t)
+template <typename T>
+__device__ inline T pendulum_choose_control(int b, const double* __restrict__ y, const int* __restrict__ sstatus,
+                                            const int* __restrict__ cstatus, const int* __restrict__ tstatus,
+                                            const T* __restrict__ u_ref, const T* __restrict__ h, T* __restrict__ u,
+                                            int* __restrict__ status, T* __restrict__ min_h, int* __restrict__ fails, int& st) {
+    st = tstatus[b] == 1 ? BCBF_PENDULUM_BADHESSIAN : cstatus[b] != 0 ? BCBF_SOCP_BADCONE : sstatus[b];
     status[b] = st;
     const T ub = st == 0 ? (T)y[(size_t)b * 3 + 2] : u_ref[b];
     u[b] = ub;
@@ -138,6 +141,41 @@ pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int
         min_h[b] = hv < min_h[b] ? hv : min_h[b];
         fails[b] += st != 0;
     }
+    return ub;
+}
+
+// The observation row of pendulum_plant_kernel<T, true>, for the sampled plant kernel: x still holds x_t, (th, om) = x_{t+1}.
+// (That kernel keeps its own copy of these lines: calling this function from it swaps two of its instructions, and the kernels of
+// the two earlier entries are held instruction-identical.)
+template <typename T>
+__device__ inline void pendulum_observation_row(const PendulumLearn<T>& L, int b, const T* __restrict__ x, T ub, T th, T om, T dt) {
+    if (L.obs_x) {
+        const T t0 = x[b * 2], w0 = x[b * 2 + 1];
+        T m0 = T(0), m1 = T(0);
+        if (L.has_mean) {
+            m0 = w0 + T(0) * ub;
+            m1 = -(L.mean_gravity / L.mean_length) * sin(t0) + T(1) / (L.mean_mass * L.mean_length) * ub;
+        }
+        const size_t r = (size_t)b * L.obs_ld * 2;
+        L.obs_x[r] = t0;
+        L.obs_x[r + 1] = w0;
+        L.obs_uh[r] = T(1);
+        L.obs_uh[r + 1] = ub;
+        L.obs_y[r] = (th - t0) / dt - m0;
+        L.obs_y[r + 1] = (om - w0) / dt - m1;
+    }
+}
+
+template <typename T, bool Learn>
+__global__ void __launch_bounds__(256)
+pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int* __restrict__ sstatus,
+                      const int* __restrict__ cstatus, const int* __restrict__ tstatus, const T* __restrict__ u_ref,
+                      const T* __restrict__ h, T* __restrict__ u, int* __restrict__ status, T* __restrict__ min_h,
+                      int* __restrict__ fails, T mass, T gravity, T length, T dt, PendulumLearn<T> L, int Bt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt) return;
+    int st;
+    const T ub = pendulum_choose_control<T>(b, y, sstatus, cstatus, tstatus, u_ref, h, u, status, min_h, fails, st);
     T th = x[b * 2], om = x[b * 2 + 1];
     pendulum_euler<T>(th, om, ub, mass, gravity, length, dt);
     if constexpr (Learn) {
@@ -159,6 +197,74 @@ pendulum_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int
             L.obs_y[r + 1] = (om - w0) / dt - m1;
         }
     }
+    x[b * 2] = th;
+    x[b * 2 + 1] = om;
+}
+
+// What the sampled entry adds: the caller's standard normals, the outputs on the draw, and what Sigma4 is made of
+template <typename T>
+struct PendulumDraw {
+    const T* z;                                 // [Bt,2,4]
+    T *xdot_s, *cbc_s;                          // [Bt,2] each, or NULL
+    int *relaxed, *viol_relaxed;                // [Bt] counters (both or neither)
+    T rho_tol;
+    int gp;                                     // 0: no learned model and no prior (Sigma4 = 0)
+    int kernel_kind;
+    const T *Mk, *Bk, *G, *Mj, *A, *Bm, *ell, *s2, *gh, *Hh, *kalpha;
+};
+
+// The plant kernel of the sampled entry: the jet columns CBC2 reads are DRAWN from the model's posterior at x_t
+// (pendulum_posterior_plant.h), the state advances on the draw -- true_* plays no part -- and the condition is evaluated on the
+// same draw at the applied control.  Bookkeeping and observation rows as pendulum_plant_kernel<T, true>.
+template <typename T>
+__global__ void __launch_bounds__(256)
+pendulum_sampled_plant_kernel(T* __restrict__ x, const double* __restrict__ y, const int* __restrict__ sstatus,
+                              const int* __restrict__ cstatus, const int* __restrict__ tstatus, const T* __restrict__ u_ref,
+                              const T* __restrict__ h, T* __restrict__ u, int* __restrict__ status, T* __restrict__ min_h,
+                              int* __restrict__ fails, T dt, PendulumLearn<T> L, PendulumDraw<T> D, int Bt) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bt) return;
+    int st;
+    const T ub = pendulum_choose_control<T>(b, y, sstatus, cstatus, tstatus, u_ref, h, u, status, min_h, fails, st);
+    double S4[4][4], LS[4][4], Ad[2][2], LA[2][2], mean[2][4], Z[2][4], S[2][4], gh[2], Hh[2][2];
+    pendulum_jet_covariance<T>(D.gp, D.Bk + (size_t)b * 4, D.G + (size_t)b * 36, D.s2[b], D.Bm[(size_t)b * 4], D.ell + (size_t)b * 2,
+                               kernel_kxx(D.kernel_kind), S4);
+    psd_chol<4>(S4, LS);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            Ad[i][j] = (double)D.A[(size_t)b * 4 + i * 2 + j];
+            Hh[i][j] = (double)D.Hh[(size_t)b * 4 + i * 2 + j];
+        }
+        gh[i] = (double)D.gh[(size_t)b * 2 + i];
+        mean[i][0] = (double)D.Mk[(size_t)b * 4 + i * 2];
+        mean[i][1] = (double)D.Mk[(size_t)b * 4 + i * 2 + 1];
+        mean[i][2] = (double)D.Mj[(size_t)b * 12 + i * 6 + 2];
+        mean[i][3] = (double)D.Mj[(size_t)b * 12 + i * 6 + 4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) Z[i][k] = (double)D.z[(size_t)b * 8 + i * 4 + k];
+    }
+    psd_chol<2>(Ad, LA);
+    pendulum_jet_draw(mean, LA, LS, Z, S);
+    double xd[2], lfh, cbc2;
+    pendulum_cbc2_on(S, (double)ub, (double)h[b], gh, Hh, (double)D.kalpha[0], (double)D.kalpha[1], xd, lfh, cbc2);
+    if (D.xdot_s) {
+        D.xdot_s[(size_t)b * 2] = (T)xd[0];
+        D.xdot_s[(size_t)b * 2 + 1] = (T)xd[1];
+    }
+    if (D.cbc_s) {
+        D.cbc_s[(size_t)b * 2] = (T)lfh;
+        D.cbc_s[(size_t)b * 2 + 1] = (T)cbc2;
+    }
+    if (D.relaxed) {      // the safety cone is soft: a step that bought slack (rho = y[1]) was never promised the risk
+        const int rel = st == 0 && (T)y[(size_t)b * 3 + 1] > D.rho_tol;
+        D.relaxed[b] += rel;
+        D.viol_relaxed[b] += rel && !(cbc2 >= 0.0);
+    }
+    T th = x[b * 2], om = x[b * 2 + 1];
+    pendulum_advance<T>(th, om, (T)xd[0], (T)xd[1], dt);
+    pendulum_observation_row<T>(L, b, x, ub, th, om, dt);
     x[b * 2] = th;
     x[b * 2 + 1] = om;
 }
@@ -190,7 +296,8 @@ static int pendulum_control_step(
     double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
     double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
     double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
-    const PendulumLearn<double>& L, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
+    const PendulumLearn<double>& L, const PendulumDraw<double>* D, int Bt, int n, int m, void* ev_start, void* ev_stop,
+    void* stream) {
     // ---- argument checks, before any HIP call
     if (Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
     if (n != 2 || m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
@@ -223,6 +330,12 @@ static int pendulum_control_step(
         if (L.obs_x && L.obs_ld < 1) return pendulum_einval("pendulum_control_step_observe: obs_ld < 1");
         if (L.has_mean && !(L.mean_mass * L.mean_length != 0.0))
             return pendulum_einval("pendulum_control_step_observe: mean model m l == 0");
+    }
+    if (D) {
+        if (!D->z) return pendulum_einval("pendulum_control_step_sampled: null z");
+        if (!D->relaxed != !D->viol_relaxed)
+            return pendulum_einval("pendulum_control_step_sampled: relaxed and viol_relaxed go together");
+        if (!(D->rho_tol >= 0.0)) return pendulum_einval("pendulum_control_step_sampled: rho_tol must be >= 0");
     }
     if (Bt == 0) return BCBF_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -263,10 +376,39 @@ static int pendulum_control_step(
     // 5. min y_1 over y = [y_1, rho, u] in Q^3 x Q^3
     const int qdims[2] = {3, 3};
     if ((rc = bcbf_coneqp_f64(P, q, Gc, hc, 3, 0, qdims, 2, y, sstatus, iters, Bt, max_iters, stream))) return rc;
-    // 6. choose u, bookkeeping, plant step
+    // 6. choose u, bookkeeping, plant step (the sampled entry: on a draw from the model's posterior at x_t)
+    if (D) {
+        PendulumDraw<double> d = *D;
+        d.gp = Lop != nullptr || (Learn && L.prior);
+        d.kernel_kind = kernel_kind;
+        d.Mk = Mk; d.Bk = Bk; d.G = G; d.Mj = Mj; d.A = A; d.Bm = Bm; d.ell = ell; d.s2 = s2; d.gh = gh; d.Hh = Hh;
+        d.kalpha = kalpha;
+        hipLaunchKernelGGL((pendulum_sampled_plant_kernel<double>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
+                           h, u, status, min_h, fails, dt, L, d, Bt);
+        return check_launch("pendulum_sampled_plant");
+    }
     hipLaunchKernelGGL((pendulum_plant_kernel<double, Learn>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
                        h, u, status, min_h, fails, true_mass, true_gravity, true_length, dt, L, Bt);
     return check_launch("pendulum_plant");
+}
+
+// the observing entries' arguments as the kernels take them
+static PendulumLearn<double> pendulum_learn_args(const double* M0, const double* s2, const double* Bm, int mean_model,
+                                                 double mean_mass, double mean_gravity, double mean_length, int prior,
+                                                 const double* explore, double eps, const double* ctrl_range, double* obs_x,
+                                                 double* obs_uh, double* obs_y, int obs_ld) {
+    PendulumLearn<double> L{};
+    L.prior = prior;
+    L.M0 = M0; L.s2 = s2; L.Bm = Bm;
+    L.explore = explore;
+    L.eps = eps;
+    L.clip = ctrl_range != nullptr;
+    L.lo = ctrl_range ? ctrl_range[0] : 0.0;
+    L.hi = ctrl_range ? ctrl_range[1] : 0.0;
+    L.obs_x = obs_x; L.obs_uh = obs_uh; L.obs_y = obs_y; L.obs_ld = obs_ld;
+    L.has_mean = mean_model != 0;
+    L.mean_mass = mean_mass; L.mean_gravity = mean_gravity; L.mean_length = mean_length;
+    return L;
 }
 
 }  // namespace bcbf
@@ -301,7 +443,7 @@ int bcbf_pendulum_control_step_f64(
         Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
         theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
         true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
-        P, q, y, sstatus, iters, u, status, min_h, fails, L, Bt, n, m, ev_start, ev_stop, stream);
+        P, q, y, sstatus, iters, u, status, min_h, fails, L, nullptr, Bt, n, m, ev_start, ev_stop, stream);
 }
 
 int bcbf_pendulum_control_step_observe_f64(
@@ -316,21 +458,36 @@ int bcbf_pendulum_control_step_observe_f64(
     double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
     int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
     int obs_ld, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
-    bcbf::PendulumLearn<double> L{};
-    L.prior = prior;
-    L.M0 = M0; L.s2 = s2; L.Bm = Bm;
-    L.explore = explore;
-    L.eps = eps;
-    L.clip = ctrl_range != nullptr;
-    L.lo = ctrl_range ? ctrl_range[0] : 0.0;
-    L.hi = ctrl_range ? ctrl_range[1] : 0.0;
-    L.obs_x = obs_x; L.obs_uh = obs_uh; L.obs_y = obs_y; L.obs_ld = obs_ld;
-    L.has_mean = mean_model != 0;
-    L.mean_mass = mean_mass; L.mean_gravity = mean_gravity; L.mean_length = mean_length;
+    const bcbf::PendulumLearn<double> L = bcbf::pendulum_learn_args(M0, s2, Bm, mean_model, mean_mass, mean_gravity, mean_length,
+                                                                    prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld);
     return bcbf::pendulum_control_step<true>(
         Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
         theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
         true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
-        P, q, y, sstatus, iters, u, status, min_h, fails, L, Bt, n, m, ev_start, ev_stop, stream);
+        P, q, y, sstatus, iters, u, status, min_h, fails, L, nullptr, Bt, n, m, ev_start, ev_stop, stream);
+}
+
+int bcbf_pendulum_control_step_sampled_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
+    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
+    const bcbf::PendulumLearn<double> L = bcbf::pendulum_learn_args(M0, s2, Bm, mean_model, mean_mass, mean_gravity, mean_length,
+                                                                    prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld);
+    bcbf::PendulumDraw<double> D{};
+    D.z = z; D.xdot_s = xdot_s; D.cbc_s = cbc_s; D.relaxed = relaxed; D.viol_relaxed = viol_relaxed; D.rho_tol = rho_tol;
+    return bcbf::pendulum_control_step<true>(
+        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
+        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
+        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
+        P, q, y, sstatus, iters, u, status, min_h, fails, L, &D, Bt, n, m, ev_start, ev_stop, stream);
 }
 }

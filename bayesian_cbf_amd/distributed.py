@@ -61,6 +61,22 @@ def reduce_risk_stats(instance_steps, violations, min_cbc, max_risk):
                 per_obstacle=[dict(violations=v, rate=v / max(n, 1)) for v in per], min_cbc=[float(v) for v in mins.tolist()])
 
 
+def reduce_cbc2_risk_stats(instance_steps, violations, min_cbc2, relaxed_steps, violations_relaxed, max_unsafe_prob):
+    """`reduce_risk_stats` for the pendulum's single rel-degree-2 condition on a posterior-drawn plant, whose safety cone is soft:
+    SUM for the solved instance-steps, the violations, the solved steps that bought slack (`relaxed_steps`) and the violations
+    among those; MIN for the smallest drawn condition.  Returns dict(instance_steps, violations, rate = violations /
+    instance_steps, max_unsafe_prob, min_cbc2, relaxed_steps, violations_relaxed, rate_unrelaxed = the rate over the steps that
+    bought no slack -- the ones the program promised the risk to)."""
+    counts = torch.stack([torch.as_tensor(v).detach().to("cpu", torch.float64).reshape(()) for v in
+                          (violations, relaxed_steps, violations_relaxed)])
+    r = reduce_risk_stats(instance_steps, counts, torch.as_tensor(min_cbc2).detach().reshape(1), max_unsafe_prob)
+    viol, relaxed, viol_relaxed = (v["violations"] for v in r["per_obstacle"])
+    n = r["instance_steps"]
+    return dict(instance_steps=n, violations=viol, rate=viol / max(n, 1), max_unsafe_prob=float(max_unsafe_prob),
+                min_cbc2=r["min_cbc"][0], relaxed_steps=relaxed, violations_relaxed=viol_relaxed,
+                rate_unrelaxed=(viol - viol_relaxed) / max(n - relaxed, 1))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # One launcher for every multi-GPU harness (bench.py = config 3, examples_mc_rollouts.py = config 4,
 # tools/bench_online.py = config 5): `python <script> --gpus N` starts N ranks itself, or runs as one rank of an external

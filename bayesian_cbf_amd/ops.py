@@ -1639,7 +1639,7 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
                                   theta_c=math.pi / 4, delta_c=math.pi / 8, k_alpha=(1.0, 3.0), x_goal=(0.0, 0.0),
                                   Q_goal=((1.0, 0.0), (0.0, 1.0)), R=1.0, u_ref=None, max_unsafe_prob=0.01, ctrl_reg=1.0,
                                   relax_weight=100.0, hessian_mode="reference", max_iters=100, stats=None, stream=None, *,
-                                  prior=False, explore=None, eps=0.0, ctrl_range=None, observe=False):
+                                  prior=False, explore=None, eps=0.0, ctrl_range=None, observe=False, sampled=None):
     """Bind every argument of `bcbf_pendulum_control_step_f64` once and return `step(ev_start=None, ev_stop=None)`.
 
     gp: dict(Lop, Vw, X, UHB, ell, s2, Bm, M0, A[, kernel]) of a learned model -- a leading axis of 1 on the GP tensors is
@@ -1660,13 +1660,21 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
       observe=True: the step writes its observation row (x_t, (1, u_t), (x_{t+1} - x_t)/dt - mean) where the call says.
     With any of them the returned step is `step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None)`: eps and
     explore replace the bound ones for this call (eps varies per step), obs = (obs_x, obs_uh, obs_y, ld) are [.,2] tensors
-    whose row b * ld is instance b's (ld = 1: [Bt,2] tensors; a column t of [Bt,T,2] stream buffers: ld = T)."""
+    whose row b * ld is instance b's (ld = 1: [Bt,2] tensors; a column t of [Bt,T,2] stream buffers: ld = T).
+
+    sampled = dict(z=[Bt,2,4], xdot_s=[Bt,2] | None, cbc_s=[Bt,2] | None[, relaxed=[Bt] int32, viol_relaxed=[Bt] int32,
+    rho_tol=1e-6]): the plant is DRAWN FROM THE MODEL'S POSTERIOR (bcbf_pendulum_control_step_sampled_f64; composes with every
+    option above, the same `step` signature).  The four jet columns the condition reads are drawn as mean + L_A z L_Sigma4' from
+    the caller's standard normals z (read at every call: refill the tensor between steps), every instance advances by
+    xdot_s = f_s + g_s u dt on the draw -- true_model is ignored -- and cbc_s = (L_f h, CBC2) on the same draw at the applied
+    control is what `rollout_risk` counts.  relaxed / viol_relaxed (together) count the solved steps whose slack rho = y[1]
+    exceeds rho_tol and the violations among them.  The observation rows then record the sampled plant."""
     from .cbc2 import cbc2_safety_factor
     Bt = x.shape[0]
     f = dict(dtype=x.dtype, device=x.device)
     if x.dtype != torch.float64:
         raise TypeError("the pendulum control step is fp64")
-    learn = bool(prior) or explore is not None or ctrl_range is not None or bool(observe)
+    learn = bool(prior) or explore is not None or ctrl_range is not None or bool(observe) or sampled is not None
     if prior and (gp is None or gp.get("Lop") is not None):
         raise ValueError("prior=True takes the hyper-parameters (ell, s2, Bm, M0, A) of a regressor without data, no Lop")
     if prior:                      # a regressor with no data: its GP prior, with its own hyper-parameters per instance
@@ -1712,7 +1720,7 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
     dev, out = x.device, ws["u"]
     fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     if learn:
-        return _pendulum_observe_step(head[:-3], keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref)
+        return _pendulum_observe_step(head[:-3], keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled)
     fn = lib.bcbf_pendulum_control_step_f64
 
     def step(ev_start=None, ev_stop=None):
@@ -1726,16 +1734,37 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
     return step
 
 
-def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref):
+def _pendulum_sampled_args(x, sampled):
+    """`pendulum_control_step_prepare(sampled=...)` checked, as the entry's (z, xdot_s, cbc_s, relaxed, viol_relaxed, rho_tol)."""
+    Bt = x.shape[0]
+    z, xdot_s, cbc_s = sampled["z"], sampled.get("xdot_s"), sampled.get("cbc_s")
+    relaxed, viol_relaxed = sampled.get("relaxed"), sampled.get("viol_relaxed")
+    _chk(x, z, xdot_s, cbc_s)
+    if z is None or tuple(z.shape) != (Bt, 2, 4):
+        raise ValueError("sampled['z'] must be a [Bt,2,4] tensor of standard-normal draws")
+    if any(v is not None and tuple(v.shape) != (Bt, 2) for v in (xdot_s, cbc_s)):
+        raise ValueError("sampled['xdot_s'] and sampled['cbc_s'] are [Bt,2]")
+    if (relaxed is None) != (viol_relaxed is None):
+        raise ValueError("sampled['relaxed'] and sampled['viol_relaxed'] are given together or not at all")
+    for v in (relaxed, viol_relaxed):
+        if v is not None and (v.dtype != torch.int32 or tuple(v.shape) != (Bt,) or v.device != x.device or not v.is_contiguous()):
+            raise ValueError("sampled['relaxed'] and sampled['viol_relaxed'] are contiguous int32 [Bt] tensors on x's device")
+    return (_p(z), _p(xdot_s), _p(cbc_s), _p(relaxed), _p(viol_relaxed), float(sampled.get("rho_tol", 1e-6)))
+
+
+def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled=None):
     """The step of `pendulum_control_step_prepare` on bcbf_pendulum_control_step_observe_f64 (head: the plain entry's
-    arguments up to `fails`)."""
+    arguments up to `fails`), or with `sampled` on bcbf_pendulum_control_step_sampled_f64."""
     if explore is not None and u_ref is not None:
         raise ValueError("explore wraps the greedy u_ref; it cannot be combined with a caller's u_ref")
     _chk(x, explore)
     rng = None if ctrl_range is None else (ctypes.c_double * 2)(*[float(v) for v in ctrl_range])
     fn, dev, Bt = lib.bcbf_pendulum_control_step_observe_f64, x.device, x.shape[0]
+    what, draw = "bcbf_pendulum_control_step_observe", ()
+    if sampled is not None:
+        fn, what, draw = lib.bcbf_pendulum_control_step_sampled_f64, "bcbf_pendulum_control_step_sampled", _pendulum_sampled_args(x, sampled)
     bound = dict(eps=float(eps), explore=explore)
-    keep = keep + (rng, explore)
+    keep = keep + (rng, explore, None if sampled is None else dict(sampled))
 
     def step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None):
         ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
@@ -1744,10 +1773,10 @@ def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_
         if explore is not None:
             _chk(x, explore)
         o = (None, None, None, 1) if obs is None else (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
-        rc = fn(*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, Bt, 2, 1, ev0, ev1,
+        rc = fn(*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, *draw, Bt, 2, 1, ev0, ev1,
                 fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc:
-            check(rc, "bcbf_pendulum_control_step_observe")
+            check(rc, what)
         return out
     step.keep = keep
     return step

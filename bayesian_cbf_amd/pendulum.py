@@ -393,14 +393,17 @@ def pendulum_bayes_cbf_safe_rollouts(Bt=4096, numSteps=250, D=400, max_train=200
     """Fit a ControlAffineRegressor on one randomised pendulum trajectory (`sampling_pendulum_data` under ControlRandom, a
     random subset of `max_train` rows, `training_iter` Adam steps: learn_dynamics_from_data, pendulum.py:345-371), then run
     `rollouts.pendulum_safety_rollouts` with that ONE model shared by all Bt instances (regime S).  Returns
-    (regressor, rollout result)."""
-    from .control_affine_model import ControlAffineRegressor
+    (regressor, rollout result).  Keywords go through to the rollouts: plant="posterior" steps every instance on plants drawn
+    from the fitted model's own posterior and adds `risk`, the empirical rate of CBC2 < 0 on the draw, to hold against
+    max_unsafe_prob (rho_tol separates the steps that bought slack)."""
+    from .control_affine_model import ControlAffineRegressorExact
     from .rollouts import pendulum_safety_rollouts
     torch.manual_seed(seed)
     pend_env = PendulumDynamicsModel(m=1, n=2, mass=mass, gravity=gravity, length=length)
     dX, X, U = sampling_pendulum_data(pend_env, D=D, x0=torch.tensor([theta0, omega0]), dt=tau,
                                       controller=ControlRandom(mass=mass, gravity=gravity, length=length).control)
-    dgp, _ = learn_dynamics_from_data(dX, X, U, pend_env, ControlAffineRegressor, None, max_train=max_train,
+    # (the Exact regressor: learn_dynamics_from_data evaluates the fit on a grid with custom_predict_fullmat, which the base class lacks)
+    dgp, _ = learn_dynamics_from_data(dX, X, U, pend_env, ControlAffineRegressorExact, None, max_train=max_train,
                                       training_iter=training_iter, device=device, dtype=torch.float64)
     gp = dict(dgp._state(), kernel=getattr(dgp, "data_kernel", "rbf"))
     kw.setdefault("true_model", (mass, gravity, length))
@@ -465,7 +468,8 @@ def pendulum_online_learning_rollouts(Bt=4096, numSteps=250, tau=0.002, theta0=7
     """run_pendulum_control_online_learning (pendulum.py:1041-1048: 250 steps, tau = 0.002, theta0 = 7 pi / 12, float64)
     with ControlPendulumCBFLearned's settings (train every 10 steps, max_train 200, egreedy (1, 0.01), ctrl_range (-15,
     15), `iterations` = 100 Adam steps per refit) and learning ON, for Bt perturbed starts at once
-    (`rollouts.pendulum_learning_rollouts`)."""
+    (`rollouts.pendulum_learning_rollouts`).  Keywords go through: plant="posterior" draws every step's plant from the model the
+    instance holds at that step (the rows it learns from then record the drawn plant) and adds `risk`."""
     from .rollouts import pendulum_learning_rollouts
     return pendulum_learning_rollouts(Bt, numSteps=numSteps, dt=tau, theta0=theta0, omega0=omega0, fit_iters=fit_iters,
                                       learning=True, **kw)

@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .cbc2 import cbc1_safety_factor
-from .distributed import reduce_risk_stats, reduce_rollout_stats
+from .distributed import reduce_cbc2_risk_stats, reduce_risk_stats, reduce_rollout_stats
 from .planner import PiecewiseLinearPlanner
 
 
@@ -1448,7 +1448,7 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
                              gp=None, shared=False, mean_model=None, true_model=(1.0, 10.0, 1.0), max_unsafe_prob=0.01,
                              k_alpha=(1.0, 3.0), cbf_col_theta=math.pi / 4, cbf_col_delta=math.pi / 8,
                              dtype=torch.float64, device="cuda", use_graph=False, record=False, seed=0, max_iters=100,
-                             hessian_mode="reference"):
+                             hessian_mode="reference", plant="true", rho_tol=1e-6):
     """Bt closed loops of the pendulum's rel-degree-2 safety filter (SOCPController with cbfs = [RadialCBFRelDegree2] and
     the greedy nominal controller, bcbf_pendulum_control_step) from perturbed start states, numSteps steps each.  The
     defaults are run_pendulum_control_online_learning's (pendulum.py:1041-1048: theta0 = 7 pi/12, tau = 0.002, 250 steps,
@@ -1460,7 +1460,24 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
     mean_model: None or the pendulum (mass, gravity, length) added to the learned mean.  A trajectory collides when
     min_h < 0 (NaN-safe: anything not provably >= 0 counts).  Statistics go through `reduce_rollout_stats` (one
     collective at the end, as C4); use_graph replays one captured step on one stream.  Returns dict(stats, x_final[Bt,2],
-    min_h[Bt], fails[Bt], traj[numSteps+1,Bt,2] (record), u[numSteps,Bt] (record), loop_seconds)."""
+    min_h[Bt], fails[Bt], traj[numSteps+1,Bt,2] (record), u[numSteps,Bt] (record), loop_seconds).
+
+    plant: "true" (default) -- the pendulum true_model -- or "posterior": every step's plant is a draw from the model's OWN
+    posterior at the visited state (`ops.pendulum_control_step_prepare` with `sampled`; true_model is ignored), the distribution
+    the program's chance constraint P(CBC2 >= 0) >= 1 - max_unsafe_prob is stated under.  For relative degree 2 the moments the
+    program works with are the reference's approximation of a quadratic form's, so whether the loop holds that probability is
+    a measurement.  The standard normals z_all[numSteps,Bt,2,4] are drawn once from the seeded device generator, after the
+    start noise; row t is gathered per step, so the same seed gives the same trajectories eager and under use_graph.  The result
+    gains risk = dict(instance_steps, violations, rate, max_unsafe_prob, min_cbc2, relaxed_steps, violations_relaxed,
+    rate_unrelaxed) (`distributed.reduce_cbc2_risk_stats`): over the solved instance-steps, how often CBC2 was negative ON THE
+    DRAW, and the same over the steps whose slack rho = y[1] stayed <= rho_tol (the safety cone is soft: a step that bought slack
+    was never promised the risk); with record also cbc_s[numSteps,Bt,2] = (L_f h, CBC2) on the draw, status[numSteps,Bt] and
+    rho[numSteps,Bt], the slack of every step.
+    Draws of different steps are independent (the marginal at each visited (x_t, u_t) is exact); a trajectory is not one
+    function drawn from the GP."""
+    if plant not in ("true", "posterior"):
+        raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    sampled = plant == "posterior"
     dev = torch.device(device)
     f = dict(dtype=dtype, device=dev)
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -1472,10 +1489,28 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
     ws = ops.pendulum_workspace(Bt, dtype, dev)
     min_h = torch.full((Bt,), float("inf"), **f)
     fails = torch.zeros(Bt, dtype=torch.int32, device=dev)
+    state = [x, min_h, fails]                        # what a step changes (saved / restored around the graph capture)
+    draw = risk = None
+    if sampled:
+        z_all = torch.randn(numSteps, Bt, 2, 4, generator=gen, **f)
+        draw, risk = _pendulum_risk_buffers(Bt, rho_tol, f)
+        state += [risk[k] for k in ("viol", "solved", "min_cbc")] + [draw["relaxed"], draw["viol_relaxed"]]
+        tctr = torch.zeros(1, dtype=torch.long, device=dev)
+        cbc_traj = torch.empty(numSteps, Bt, 2, **f) if record else None
+        status_traj = torch.empty(numSteps, Bt, dtype=torch.int32, device=dev) if record else None
+        rho_traj = torch.empty(numSteps, Bt, **f) if record else None
     step = ops.pendulum_control_step_prepare(gp, ws, x, mean_model=mean_model, true_model=true_model, dt=dt,
                                              theta_c=cbf_col_theta, delta_c=cbf_col_delta, k_alpha=k_alpha,
                                              max_unsafe_prob=max_unsafe_prob, max_iters=max_iters,
-                                             hessian_mode=hessian_mode, stats=(min_h, fails))
+                                             hessian_mode=hessian_mode, stats=(min_h, fails), sampled=draw)
+
+    def one_step(t=None):
+        if sampled:      # this step's draws (t: a python int, or the device counter inside the captured graph), then the risk counters
+            draw["z"].copy_(z_all.index_select(0, t)[0] if torch.is_tensor(t) else z_all[t])
+        step()
+        if sampled:
+            ops.rollout_risk(draw["cbc_s"], ws["status"], risk["viol"], risk["solved"], risk["min_cbc"])
+
     traj = torch.empty(numSteps + 1, Bt, 2, **f) if record else None
     us = torch.empty(numSteps, Bt, **f) if record else None
     if record:
@@ -1484,14 +1519,16 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
     graph = None
     if use_graph and not record:
         side = torch.cuda.Stream(device=dev)
-        saved = [v.clone() for v in (x, min_h, fails)]
+        saved = [v.clone() for v in state]
         with torch.cuda.stream(side):                   # warm-up on the capture stream
-            step()
+            one_step(tctr if sampled else None)
         side.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
-            step()
-        for dst, src in zip((x, min_h, fails), saved):      # the warm-up advanced the state: restore it
+            one_step(tctr if sampled else None)
+            if sampled:
+                tctr.add_(1)
+        for dst, src in zip(state, saved):      # the warm-up advanced the state: restore it
             dst.copy_(src)
         torch.cuda.synchronize(dev)
     t_loop = time.perf_counter()
@@ -1499,15 +1536,37 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
         if graph is not None:
             graph.replay()
         else:
-            step()
+            one_step(t)
         if record:
             traj[t + 1] = x
             us[t] = ws["u"][:, 0]
+            if sampled:
+                cbc_traj[t] = draw["cbc_s"]
+                status_traj[t] = ws["status"]
+                rho_traj[t] = ws["y"][:, 1]
     torch.cuda.synchronize(dev)
     t_loop = time.perf_counter() - t_loop
     collided = ~(min_h >= 0)
     stats = reduce_rollout_stats(collided.sum(), min_h.min(), 0.0, (fails > 0).sum(), Bt)
-    return dict(stats=stats, x_final=x, min_h=min_h, fails=fails, traj=traj, u=us, loop_seconds=t_loop, ws=ws)
+    out = dict(stats=stats, x_final=x, min_h=min_h, fails=fails, traj=traj, u=us, loop_seconds=t_loop, ws=ws)
+    if sampled:
+        out.update(risk=_pendulum_risk_result(draw, risk, max_unsafe_prob), cbc_s=cbc_traj, status=status_traj, rho=rho_traj)
+    return out
+
+
+def _pendulum_risk_buffers(Bt, rho_tol, f):
+    """(`sampled` of `ops.pendulum_control_step_prepare`, the counters of `ops.rollout_risk` with Kob = 1) of a pendulum loop
+    on a posterior-drawn plant."""
+    i = dict(dtype=torch.int32, device=f["device"])
+    draw = dict(z=torch.empty(Bt, 2, 4, **f), xdot_s=torch.zeros(Bt, 2, **f), cbc_s=torch.zeros(Bt, 2, **f),
+                relaxed=torch.zeros(Bt, **i), viol_relaxed=torch.zeros(Bt, **i), rho_tol=float(rho_tol))
+    risk = dict(viol=torch.zeros(Bt, 1, **i), solved=torch.zeros(Bt, **i), min_cbc=torch.full((Bt, 1), float("inf"), **f))
+    return draw, risk
+
+
+def _pendulum_risk_result(draw, risk, max_unsafe_prob):
+    return reduce_cbc2_risk_stats(risk["solved"].sum(), risk["viol"].sum(), risk["min_cbc"].min(), draw["relaxed"].sum(),
+                                  draw["viol_relaxed"].sum(), max_unsafe_prob)
 
 
 def pendulum_learning_schedule(numSteps, train_every=10, max_train=200):
@@ -1528,7 +1587,7 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
                                start_noise=0.05, true_model=(1.0, 10.0, 1.0), max_unsafe_prob=0.01, k_alpha=(1.0, 3.0),
                                cbf_col_theta=math.pi / 4, cbf_col_delta=math.pi / 8, fit_lr=0.1,
                                gamma_length_scale_prior=(math.pi / 100, math.pi / 100), max_iters=100,
-                               hessian_mode="reference", device="cuda"):
+                               hessian_mode="reference", device="cuda", plant="true", rho_tol=1e-6):
     """Bt closed loops of the pendulum that LEARN their dynamics while the safety filter drives them
     (ControlPendulumCBFLearned, pendulum.py:909-961, through ControlCBFLearned / MeanAdjustedModel, controllers.py:320-378,
     665-736; the settings of run_pendulum_control_online_learning, pendulum.py:1041-1048), fp64, regime I: every instance
@@ -1561,10 +1620,16 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
     fit_jitter / fit_target, one [Bt,N] / [Bt,N,2] rand per iteration)): replayed
     instead of drawn (a column slice of them is a sub-batch's).  x0: [Bt,2] start states (default (theta0, omega0) +
     start_noise randn).
+    plant="posterior" (as `pendulum_safety_rollouts`): every step's plant is a draw from the model the instance holds at that
+    step -- the prior until the first refit -- so the rows the loop learns from record the drawn plant; z_all[T,Bt,2,4] is drawn
+    after explore (and is not part of `draws`); the result gains `risk`, with record also cbc_s[T,Bt,2].
     Returns dict(stats (`reduce_rollout_stats`), report, x_final, min_h, fails; record: traj[T+1,Bt,2], u[T,Bt],
     u_ref[T,Bt], status[T,Bt], draws, rows = the stream buffers (X, UH, Y [Bt,T,2]), final = dict(X, UH, Y, jitter [Bt,N,.]
     of the last refit, hyper, gp = the model the loop ended with))."""
     from .controllers import epsilon
+    if plant not in ("true", "posterior"):
+        raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    sampled = plant == "posterior"
     dev = torch.device(device)
     f = dict(dtype=torch.float64, device=dev)
     n, C = 2, 2
@@ -1618,6 +1683,10 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
     kw = dict(mean_model=mean_model, true_model=true_model, dt=dt, theta_c=cbf_col_theta, delta_c=cbf_col_delta,
               k_alpha=k_alpha, max_unsafe_prob=max_unsafe_prob, max_iters=max_iters, hessian_mode=hessian_mode,
               stats=(min_h, fails), ctrl_range=ctrl_range, observe=True)
+    if sampled:
+        z_all = torch.randn(numSteps, Bt, 2, 4, generator=gen, **f)
+        draw, risk = _pendulum_risk_buffers(Bt, rho_tol, f)
+        kw["sampled"] = draw
     ex = explore[0] if egreedy is not None else None          # (each call passes its step's [Bt,2] slice)
     step = ops.pendulum_control_step_prepare(dict(hyper), ws, x, prior=True, explore=ex, **kw)
     model = None
@@ -1626,6 +1695,8 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
         rec = dict(traj=torch.empty(numSteps + 1, Bt, 2, **f), u=torch.empty(numSteps, Bt, **f),
                    u_ref=torch.empty(numSteps, Bt, **f), status=torch.empty(numSteps, Bt, dtype=torch.int32, device=dev))
         rec["traj"][0] = x
+        if sampled:
+            rec["cbc_s"] = torch.empty(numSteps, Bt, 2, **f)
     E_ = lambda: torch.cuda.Event(enable_timing=True)
     ev_refit = [(E_(), E_()) for _ in schedule]
     refits, final = [], None
@@ -1634,7 +1705,13 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
     k = 0
     for t in range(numSteps):
         eps = epsilon(t, interpolate={0: egreedy[0], numSteps: egreedy[1]}) if egreedy is not None else 0.0
+        if sampled:
+            draw["z"].copy_(z_all[t])
         step(eps=eps, explore=explore[t] if ex is not None else None, obs=(Xall[:, t], UHall[:, t], Yall[:, t], numSteps))
+        if sampled:
+            ops.rollout_risk(draw["cbc_s"], ws["status"], risk["viol"], risk["solved"], risk["min_cbc"])
+            if record:
+                rec["cbc_s"][t] = draw["cbc_s"]
         if record:
             rec["traj"][t + 1] = x
             rec["u"][t] = ws["u"][:, 0]
@@ -1704,6 +1781,8 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
                   refit_failures_after_retries=int(fail_count),
                   instances_factored_per_retry_level=[int(v) for v in retry_counts.tolist()], refits=refits)
     out = dict(stats=stats, report=report, x_final=x, min_h=min_h, fails=fails, ws=ws)
+    if sampled:
+        out["risk"] = _pendulum_risk_result(draw, risk, max_unsafe_prob)
     if record:
         out.update(rec)
         out["draws"] = dict(explore=explore, refits=refit_draws)

@@ -1102,6 +1102,50 @@ int bcbf_pendulum_control_step_observe_f64(
     int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
     int obs_ld, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
 
+/* The same step on a plant DRAWN FROM THE MODEL'S OWN POSTERIOR, and the rel-degree-2 condition evaluated on that draw.  The
+ * program of the step asks that CBC2(x, u) = grad(L_f h)' (f + g u) + k_alpha[0] h + k_alpha[1] L_f h, L_f h = grad h' f, hold
+ * with probability >= 1 - max_unsafe_prob.  CBC2 is a QUADRATIC form in the joint posterior of f, g and the Jacobian of f, and
+ * the (mean, var) bcbf_cbc2_terms hands the program are the reference's approximation of that form's moments (both kernel
+ * arguments move in the derivative, the cross term is frozen at u_ref, the product variance is 2 tr(C)^2), so Cantelli's bound
+ * is no theorem here; this entry is the instrument that measures what the loop holds.  The launches of
+ * bcbf_pendulum_control_step_observe_f64 up to the plant kernel, then for EVERY instance
+ *     s = (f, g, df/dtheta, df/domega) ~ matrix-variate normal, mean [Mk[:,0], Mk[:,1], Mj[:,(1+0)C], Mj[:,(1+1)C]] (after the
+ *         task kernel has added the mean model), covariance A (x) Sigma4 over (state component) x (column);
+ *     Sigma4 = rows / columns {0, 1, C, 2C} of Sigma6 = P6 - G,  P6 = blockdiag(s2 Bm, kxx s2/ell_0^2 Bm, kxx s2/ell_1^2 Bm),
+ *         kxx = 1, 5/3, 8/3 for kernel_kind 0, 1, 2 (the values bcbf_cbc2_terms uses), the top-left block read from Bk;
+ *         Sigma4 = 0 without a GP; in prior mode G = 0 and Sigma4 is the prior.  The marginal of a Gaussian is exact, so the
+ *         g-derivative columns are not drawn;
+ *     S = mean + L_A Z L_Sigma' with Z = z[b] (2 x 4) and both factors a positive-semidefinite Cholesky (a pivot <= 0 zeroes
+ *         its column: a semidefinite A or Sigma4 is accepted and the draw stays in its range);
+ *     xdot_s = f_s + g_s u,   cbc_s[b] = (grad h' f_s,  (Hh f_s + J_s' grad h)' xdot_s + k_alpha[0] h + k_alpha[1] grad h' f_s)
+ *         with u the APPLIED control (y[2] where status == 0, u_ref elsewhere: an unsolved instance is driven by u_ref on the
+ *         draw and its condition is evaluated there);
+ *     x += xdot_s dt with the theta wrap of bcbf_pendulum_plant_step; true_mass, true_gravity, true_length are ignored.
+ * fp64 arithmetic in registers on the stored values, each output rounded once.  min_h / fails and the observation rows behave
+ * as in the observing entry; the rows then record the sampled plant.  Draws of different steps are independent: the marginal at
+ * every visited (x_t, u_t) is exact, which is all the per-step chance constraint speaks about; a function-consistent draw along
+ * a trajectory would have to condition on the earlier draws and is not what this entry does.
+ * Every argument of bcbf_pendulum_control_step_observe_f64, plus
+ *   z[Bt,2,4]     standard-normal draws, the caller's: the library draws no random numbers (as bcbf_subsample_rows);
+ *   xdot_s[Bt,2], cbc_s[Bt,2]   outputs, each may be NULL; cbc_s is what bcbf_rollout_risk (Kob = 1) counts;
+ *   relaxed[Bt], viol_relaxed[Bt] (int32, both or neither), rho_tol (HOST, >= 0): the safety cone is soft, and a step that bought
+ *     slack was never promised the risk -- relaxed += (status == 0 && y[1] > rho_tol), viol_relaxed += (that && !(cbc2_s >= 0)).
+ * BCBF_EINVAL, before any HIP call, for every refusal of the observing entry and: z == NULL, one counter without the other,
+ * rho_tol < 0 or NaN. */
+int bcbf_pendulum_control_step_sampled_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
+    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
+
 /* ---- The pendulum's CLF-CBF quadratic program on the KNOWN model (PendulumCBFCLFDirect, run_pendulum_control_cbf_clf:
  * pendulum.py:530-640, 770-906, 1019-1024).  Two rows, affine in the control, on the controller's model (m, g, l) at
  * x = (theta, omega), d = theta - theta_c:

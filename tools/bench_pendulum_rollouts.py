@@ -3,7 +3,9 @@
 coneqp -> plant step), fp64, N = 512 training points, 250 closed-loop steps per configuration: regime S (one model
 queried by every instance) at Bt = 4096 and 32768, regime I (one model per instance) at Bt = 4096.  One JSON line per
 configuration: instance-steps/s of the eager loop (one host call per step) and of the HIP-graph replay, and the share of
-the step the jets launch takes (events around it, eager loop)."""
+the step the jets launch takes (events around it, eager loop).
+--plant posterior: the same loops on plants drawn from the model's own posterior (bcbf_pendulum_control_step_sampled_f64); each
+line then carries the step time next to the true-plant loop's and the empirical risk of the drawn rel-degree-2 condition."""
 import json
 import math
 import os
@@ -55,11 +57,41 @@ def jets_share(gp, Bt, steps=50):
     return jets / e0.elapsed_time(e1), jets / steps
 
 
-def main(configs=(("S", 4096), ("S", 32768), ("I", 4096))):
+def posterior_line(regime, Bt, N, steps, kw, repeats=3):
+    """One JSON line: the loop on posterior-drawn plants against the same loop on the true plant, the two alternated `repeats`
+    times in this process (medians, with every repeat beside them), eager and graph, and the posterior loop's risk."""
+    for plant in ("true", "posterior"):
+        pendulum_safety_rollouts(Bt, **dict(kw, numSteps=20, plant=plant))         # warm-up (clocks, lazy loads)
+    ms = {(plant, how): [] for plant in ("true", "posterior") for how in ("eager", "graph")}
+    for _ in range(repeats):
+        for plant in ("true", "posterior"):
+            eager = pendulum_safety_rollouts(Bt, plant=plant, **kw)
+            graph = pendulum_safety_rollouts(Bt, plant=plant, use_graph=True, **kw)
+            ms[plant, "eager"].append(eager["loop_seconds"] * 1e3 / steps)
+            ms[plant, "graph"].append(graph["loop_seconds"] * 1e3 / steps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    line = dict(regime=regime, Bt=Bt, N=N, dtype="float64", steps=steps, plant="posterior", repeats=repeats,
+                eager_ms_per_step=med["posterior", "eager"], graph_ms_per_step=med["posterior", "graph"],
+                true_plant_eager_ms_per_step=med["true", "eager"], true_plant_graph_ms_per_step=med["true", "graph"],
+                graph_ms_added=med["posterior", "graph"] - med["true", "graph"],
+                all_ms_per_step={"%s_%s" % k: v for k, v in ms.items()},
+                risk=eager["risk"], collisions=eager["stats"]["collisions"],
+                instances_with_failed_programs=eager["stats"]["solver_failures"],
+                graph_equals_eager=bool(torch.equal(eager["x_final"], graph["x_final"])))
+    print(json.dumps(line), flush=True)
+    return line
+
+
+def main(configs=(("S", 4096), ("S", 32768), ("I", 4096)), plant="true"):
     N, steps = 512, int(os.environ.get("BCBF_PEND_STEPS", "250"))
     for regime, Bt in configs:
         gp = model(1 if regime == "S" else Bt, N)
         kw = dict(numSteps=steps, gp=gp, shared=regime == "S")
+        if plant == "posterior":
+            posterior_line(regime, Bt, N, steps, kw)
+            del gp
+            torch.cuda.empty_cache()
+            continue
         pendulum_safety_rollouts(Bt, **dict(kw, numSteps=20))                     # warm-up (clocks, lazy loads)
         eager = pendulum_safety_rollouts(Bt, **kw)
         graph = pendulum_safety_rollouts(Bt, use_graph=True, **kw)
@@ -77,6 +109,10 @@ def main(configs=(("S", 4096), ("S", 32768), ("I", 4096))):
 
 
 if __name__ == "__main__":
-    # --only S:4096 (repeatable): a subset of the configurations (profiling runs)
-    only = [a.split(":") for a in sys.argv[sys.argv.index("--only") + 1:]] if "--only" in sys.argv else None
-    main(tuple((r, int(b)) for r, b in only) if only else ((("S", 4096), ("S", 32768), ("I", 4096))))
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--only", nargs="+", metavar="REGIME:BT", help="a subset of the configurations, e.g. S:4096 (profiling runs)")
+    ap.add_argument("--plant", choices=("true", "posterior"), default="true")
+    args = ap.parse_args()
+    only = [a.split(":") for a in args.only] if args.only else None
+    main(tuple((r, int(b)) for r, b in only) if only else ((("S", 4096), ("S", 32768), ("I", 4096))), plant=args.plant)
