@@ -46,6 +46,13 @@ _SIGS = {
                                                + [c_int] * 2 + [c_double] * 4 + [P] * 24
                                                + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
                                                + [P] * 5 + [c_double] + [c_int] * 3 + [P] * 3),
+    # the sampled entry's arguments, then (nominal, numSteps, t, t_dev, lstatus): LQRController in place of GreedyController
+    # (controllers.py:64-115, 681)
+    "bcbf_pendulum_control_step_nominal_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
+                                                       ctypes.POINTER(c_double), c_double, P] + [c_double] * 3
+                                               + [c_int] * 2 + [c_double] * 4 + [P] * 24
+                                               + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
+                                               + [P] * 5 + [c_double] + [c_int] * 3 + [P, P] + [c_int] * 3 + [P] * 3),
 }
 # the trigger-step entries: the event's 35 arguments, the 19 of the audit group, the 9 of the observe group, (Bt, Bh, Kob, Nte, P, stream)
 _TS_EVENT = [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11
@@ -123,6 +130,8 @@ _TSIGS = {
     "bcbf_pendulum_clf_cbf_control": [P, P, c_int, "T", "PT", "T", "T", "T", c_int, "T"] + [P] * 6 + [c_int, P],
     "bcbf_pendulum_clf_cbf_rollout": [P, P, c_int, P, c_int, "T", "PT", "T", "T", "T", c_int, "T", "T"] + [P] * 5
                                      + [c_int] * 4 + [P],
+    # LQRController.control (controllers.py:64-115) and the two bdlqr LinearSystem solves inside it; x_goal, Q, R: HOST values
+    "bcbf_lqr_nominal": [P, P, P, "PT", "PT", "PT", "T", c_int, c_int, P, P, P, P, c_int, c_int, c_int, P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],
     "bcbf_unicycle_control_step": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
     "bcbf_unicycle_control_step_matern52": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],

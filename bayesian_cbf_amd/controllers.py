@@ -7,8 +7,10 @@ takes one state like the reference, or a batch x[b, n] (one program per row, one
 
 The small host-side nominal controllers (Zero / Greedy / epsilon-greedy, controllers.py:166-213, 269-285) and
 `NamedAffineFunc` (:739-771) are here as upstream has them; `ControlCBFLearned()` is constructible with its defaults
-(nominal controller = the greedy one-step tracker inside the epsilon-greedy explorer).  Not mirrored (SURVEY 2.1 #8:
-outside the GP / conic-program path): LQR / ILQR (they need the external `lqr` / `mpc` packages) and the plotters."""
+(nominal controller = the greedy one-step tracker inside the epsilon-greedy explorer).  `LQRController` (:64-115, upstream's
+default nominal controller) runs its Riccati recursion on the device (`bcbf_lqr_nominal_*`) in place of the external `bdlqr`
+package.  Not mirrored (outside the GP / conic-program path): ILQR / ILQRController (upstream never
+instantiates the former; the latter needs the external `mpc` package) and the plotters."""
 import math
 import random
 from abc import ABC, abstractmethod
@@ -103,6 +105,67 @@ class GreedyController(Controller):
             u = torch.linalg.solve(Q, c).squeeze(-1)
             assert u.shape[-1] == self.R.shape[-1]
             return u[0] if x.dim() == 1 else u
+
+
+def _autograd_jets(model, xb, n, m):
+    """Mk[b,n,1+m], Mj[b,n,(1+m)(1+n)] of a differentiable control-affine model (f_func, g_func) in the jets' layout:
+    [f | g] and their x-Jacobians by autograd, one state at a time (t_jac in LQRController.control, controllers.py:77-79)."""
+    b, C = xb.shape[0], 1 + m
+    fg = lambda z: torch.cat([torch.as_tensor(model.f_func(z), dtype=z.dtype, device=z.device).reshape(n, 1),
+                              torch.as_tensor(model.g_func(z), dtype=z.dtype, device=z.device).reshape(n, m)], dim=1)
+    Mk, Mj = xb.new_zeros(b, n, C), xb.new_zeros(b, n, C * (1 + n))
+    for i in range(b):
+        xi = xb[i].detach().clone()
+        Mk[i] = fg(xi).detach()
+        J = torch.autograd.functional.jacobian(fg, xi)                     # [n, C, n]: d [f | g]_{i c} / d x_d
+        Mj[i, :, C:] = J.permute(0, 2, 1).reshape(n, n * C)                # column (1 + d) C + c
+    return Mk, Mj
+
+
+class LQRController(Controller):
+    """Finite-horizon LQR on the model linearised at x (controllers.py:64-115; upstream's default nominal controller of
+    ControlCBFLearned, :681), on the device: `ops.lqr_nominal` (bcbf_lqr_nominal_*).  Upstream hands the linearisation to the
+    external `bdlqr` package; the recursion here is affine_backpropagation's (ilqr.py:43-76), the same author's statement of it.
+    Two backward passes of numSteps - t iterations, the second linearised at the first's control; no clipping (ctrl_range is
+    stored, as upstream, and not applied).  The Jacobians come from the jets launch for a `ControlAffineRegressor` or a sum of
+    models with one (`MeanAdjustedModel`; its deterministic summands by autograd), from autograd for any other differentiable
+    model with f_func / g_func.  x is one state [n] or a batch [B,n]."""
+
+    def __init__(self, model, x_quad_goal_cost, u_quad_cost, x_goal, numSteps, dt, ctrl_range):
+        self.x_goal, self.model = x_goal, model
+        self.Q, self.R = to_numpy(x_quad_goal_cost), to_numpy(u_quad_cost)
+        self.numSteps, self.dt, self.ctrl_range = numSteps, dt, ctrl_range
+        self.last_status = None
+
+    def jets(self, xb):
+        """(Mk, Mj) of the model at xb[b,n] in the jets' layout, on the device."""
+        from .cbc2 import FixedKernelGP, posterior_for, resolve_model
+        n, m = xb.shape[1], np.asarray(self.R).shape[-1]
+        try:
+            reg, dets = resolve_model(self.model)
+        except TypeError:
+            reg, dets = None, [self.model]
+        if reg is None or isinstance(reg, FixedKernelGP):
+            if not torch.cuda.is_available():
+                raise RuntimeError("bayesian_cbf_amd runs its arithmetic in libbcbf on a ROCm GPU; there is no CPU path")
+            xb = xb.to("cuda") if not xb.is_cuda else xb
+            Mk, Mj = xb.new_zeros(xb.shape[0], n, 1 + m), xb.new_zeros(xb.shape[0], n, (1 + m) * (1 + n))
+        else:
+            xb = reg._ensure_device_dtype(xb).contiguous()
+            _, Mk, _, _, Mj = posterior_for(reg, xb, jets=True)
+        for d in dets:
+            dk, dj = _autograd_jets(d, xb, n, m)
+            Mk, Mj = Mk + dk, Mj + dj
+        return xb.contiguous(), Mk.contiguous(), Mj.contiguous()
+
+    def control(self, x, t=None):
+        """u[m] (or [B,m]) at step t; t = None means t = 0, the full horizon numSteps (upstream fails on None)."""
+        xb = x.detach().reshape(-1, x.shape[-1])
+        xb, Mk, Mj = self.jets(xb)
+        u, status = ops.lqr_nominal(Mk, Mj, xb, to_numpy(self.x_goal), self.Q, self.R, self.dt, self.numSteps, 0 if t is None else int(t))
+        self.last_status = status
+        u = u.to(dtype=x.dtype, device=x.device)
+        return u[0] if x.dim() == 1 else u
 
 
 class EpsilonGreedyController(ABC):
@@ -404,8 +467,8 @@ class ControlCBFLearned(Controller):
                  summary_writer=None, x0=None, ctrl_reg=1., clf_relax_weight=100., enable_learning=False,
                  mean_dynamics_model_class=None, max_train=None, controller_class=QPController, planner_class=None,
                  training_iter=100):
-        """Defaults as upstream, except: the nominal controller defaults to `GreedyController` (upstream: `LQRController`,
-        which needs the external `lqr` package), goal and costs default to the origin / identity when not given (upstream:
+        """Defaults as upstream, except: the nominal controller defaults to `GreedyController` (upstream: `LQRController`;
+        pass `unsafe_controller_class=LQRController` for upstream's -- it runs on the device, `ops.lqr_nominal`), goal and costs default to the origin / identity when not given (upstream:
         `torch.tensor(None)` raises), `model=None` builds a `ControlAffineRegressorExact`, `mean_dynamics_model_class=None` a
         zero prior mean, and `exploration_controller_class=None` means "no exploration wrapper"."""
         self.x_dim, self.u_dim, self.model, self.dt, self.numSteps = x_dim, u_dim, model, dt, numSteps

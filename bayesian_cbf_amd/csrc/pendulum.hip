@@ -21,6 +21,7 @@
 #include "bcbf_common.h"
 #include "pendulum_plant.h"      // pendulum_euler, pendulum_advance
 #include "pendulum_posterior_plant.h"      // the sampled plant kernel's draw
+#include "lqr.h"                 // lqr_nominal_step_f64: the LQR nominal control (nominal = 1)
 
 namespace bcbf {
 
@@ -280,6 +281,13 @@ pendulum_plant_step_kernel(T* __restrict__ x, const T* __restrict__ u, T mass, T
     x[b * 2 + 1] = om;
 }
 
+// What the nominal entry adds: which nominal controller, and the LQR's horizon (bcbf_lqr_nominal_f64's numSteps, t, t_dev, status)
+struct PendulumNominal {
+    int nominal, numSteps, t;
+    const int* t_dev;
+    int* lstatus;
+};
+
 static int pendulum_einval(const char* why) {
     set_error_message(why);
     return BCBF_EINVAL;
@@ -297,7 +305,7 @@ static int pendulum_control_step(
     double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
     double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
     const PendulumLearn<double>& L, const PendulumDraw<double>* D, int Bt, int n, int m, void* ev_start, void* ev_stop,
-    void* stream) {
+    void* stream, const PendulumNominal* Nm = nullptr) {
     // ---- argument checks, before any HIP call
     if (Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
     if (n != 2 || m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
@@ -337,6 +345,14 @@ static int pendulum_control_step(
             return pendulum_einval("pendulum_control_step_sampled: relaxed and viol_relaxed go together");
         if (!(D->rho_tol >= 0.0)) return pendulum_einval("pendulum_control_step_sampled: rho_tol must be >= 0");
     }
+    const bool lqr = Nm && Nm->nominal == 1;
+    if (Nm) {
+        if (Nm->nominal != 0 && Nm->nominal != 1) return pendulum_einval("pendulum_control_step_nominal: nominal must be 0 or 1");
+        if (lqr && u_ref_in) return pendulum_einval("pendulum_control_step_nominal: the LQR nominal control excludes u_ref_in");
+        if (lqr && !Nm->lstatus) return pendulum_einval("pendulum_control_step_nominal: the LQR nominal control needs lstatus");
+        if (lqr && Nm->numSteps < 1) return pendulum_einval("pendulum_control_step_nominal: numSteps < 1");
+        if (lqr && !Nm->t_dev && Nm->t < 0) return pendulum_einval("pendulum_control_step_nominal: t < 0 without t_dev");
+    }
     if (Bt == 0) return BCBF_OK;
     hipStream_t st = (hipStream_t)stream;
     // 1. jets of the learned model at x (skipped without one: the task kernel writes the mean model alone)
@@ -363,6 +379,11 @@ static int pendulum_control_step(
     hipLaunchKernelGGL((pendulum_task_kernel<double, Learn>), grid, block, 0, st, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref_in,
                        u_ref, P, q, p, L, Bt);
     if ((rc = check_launch("pendulum_task"))) return rc;
+    // 2b. LQRController in place of the task kernel's greedy u_ref, on the factors it has just shifted: bcbf_lqr_nominal_f64's
+    // kernel, then the explorer's draw and the clip as the task kernel applies them
+    if (lqr && (rc = lqr_nominal_step_f64(Mk, Mj, x, x_goal, Q_goal, R, dt, Nm->numSteps, Nm->t, Nm->t_dev, L.explore, L.eps,
+                                          L.clip, L.lo, L.hi, u_ref, Nm->lstatus, Bt, stream)))
+        return rc;
     // 3. rel-degree-2 terms (linearised at u_ref), 4. the program's rows (objective cone + safety cone of kind 1)
     if ((rc = bcbf_cbc2_terms_f64(Mk, Bk, G, Mj, A, Bm, ell, s2, h, gh, Hh, kalpha, u_ref, terms2, tstatus, Bt, 2, 1,
                                   hessian_mode, kernel_kind, stream)))
@@ -489,5 +510,31 @@ int bcbf_pendulum_control_step_sampled_f64(
         theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
         true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
         P, q, y, sstatus, iters, u, status, min_h, fails, L, &D, Bt, n, m, ev_start, ev_stop, stream);
+}
+
+int bcbf_pendulum_control_step_nominal_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
+    int nominal, int numSteps, int t, const int* t_dev, int* lstatus,
+    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
+    const bcbf::PendulumLearn<double> L = bcbf::pendulum_learn_args(M0, s2, Bm, mean_model, mean_mass, mean_gravity, mean_length,
+                                                                    prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld);
+    bcbf::PendulumDraw<double> D{};
+    D.z = z; D.xdot_s = xdot_s; D.cbc_s = cbc_s; D.relaxed = relaxed; D.viol_relaxed = viol_relaxed; D.rho_tol = rho_tol;
+    const bcbf::PendulumNominal Nm{nominal, numSteps, t, t_dev, lstatus};
+    return bcbf::pendulum_control_step<true>(
+        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
+        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
+        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
+        P, q, y, sstatus, iters, u, status, min_h, fails, L, z ? &D : nullptr, Bt, n, m, ev_start, ev_stop, stream, &Nm);
 }
 }

@@ -1639,7 +1639,8 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
                                   theta_c=math.pi / 4, delta_c=math.pi / 8, k_alpha=(1.0, 3.0), x_goal=(0.0, 0.0),
                                   Q_goal=((1.0, 0.0), (0.0, 1.0)), R=1.0, u_ref=None, max_unsafe_prob=0.01, ctrl_reg=1.0,
                                   relax_weight=100.0, hessian_mode="reference", max_iters=100, stats=None, stream=None, *,
-                                  prior=False, explore=None, eps=0.0, ctrl_range=None, observe=False, sampled=None):
+                                  prior=False, explore=None, eps=0.0, ctrl_range=None, observe=False, sampled=None,
+                                  nominal="greedy", numSteps=None, t=0, t_dev=None, lstatus=None, nominal_entry=False):
     """Bind every argument of `bcbf_pendulum_control_step_f64` once and return `step(ev_start=None, ev_stop=None)`.
 
     gp: dict(Lop, Vw, X, UHB, ell, s2, Bm, M0, A[, kernel]) of a learned model -- a leading axis of 1 on the GP tensors is
@@ -1668,13 +1669,33 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
     the caller's standard normals z (read at every call: refill the tensor between steps), every instance advances by
     xdot_s = f_s + g_s u dt on the draw -- true_model is ignored -- and cbc_s = (L_f h, CBC2) on the same draw at the applied
     control is what `rollout_risk` counts.  relaxed / viol_relaxed (together) count the solved steps whose slack rho = y[1]
-    exceeds rho_tol and the violations among them.  The observation rows then record the sampled plant."""
+    exceeds rho_tol and the violations among them.  The observation rows then record the sampled plant.
+
+    nominal="lqr" (with numSteps; t=0 or t_dev, an int32 device tensor [1] the kernel reads; lstatus[Bt] int32, allocated when
+    None and returned as step.lstatus): the nominal control is the reference's LQRController (`lqr_nominal`, horizon
+    max(numSteps - t, 1)) on the mean-shifted jets instead of GreedyController, then explore and clip as above
+    (bcbf_pendulum_control_step_nominal_f64; composes with every option, excludes u_ref).  The step takes `t=` per call.
+    nominal_entry=True runs nominal="greedy" through that entry too (nominal = 0: the observing / sampled entry bit for bit)."""
     from .cbc2 import cbc2_safety_factor
     Bt = x.shape[0]
     f = dict(dtype=x.dtype, device=x.device)
     if x.dtype != torch.float64:
         raise TypeError("the pendulum control step is fp64")
-    learn = bool(prior) or explore is not None or ctrl_range is not None or bool(observe) or sampled is not None
+    if nominal not in ("greedy", "lqr"):
+        raise ValueError("nominal must be 'greedy' or 'lqr', got %r" % (nominal,))
+    nom = None
+    if nominal == "lqr":
+        if numSteps is None or u_ref is not None:
+            raise ValueError("nominal='lqr' needs numSteps (the LQR horizon) and excludes a caller's u_ref")
+        if lstatus is None:
+            lstatus = torch.zeros(Bt, dtype=torch.int32, device=x.device)
+        for name, v, size in (("t_dev", t_dev, 1), ("lstatus", lstatus, Bt)):
+            if v is not None and (v.dtype != torch.int32 or v.device != x.device or v.numel() != size or not v.is_contiguous()):
+                raise ValueError("%s must be a contiguous int32 tensor of %d element(s) on x's device" % (name, size))
+        nom = dict(code=1, numSteps=int(numSteps), t=int(t), t_dev=t_dev, lstatus=lstatus)
+    elif nominal_entry:            # the greedy controller through the nominal entry (bit for bit the observing / sampled entry)
+        nom = dict(code=0, numSteps=1, t=0, t_dev=None, lstatus=None)
+    learn = bool(prior) or explore is not None or ctrl_range is not None or bool(observe) or sampled is not None or nom is not None
     if prior and (gp is None or gp.get("Lop") is not None):
         raise ValueError("prior=True takes the hyper-parameters (ell, s2, Bm, M0, A) of a regressor without data, no Lop")
     if prior:                      # a regressor with no data: its GP prior, with its own hyper-parameters per instance
@@ -1720,7 +1741,7 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
     dev, out = x.device, ws["u"]
     fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     if learn:
-        return _pendulum_observe_step(head[:-3], keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled)
+        return _pendulum_observe_step(head[:-3], keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled, nom)
     fn = lib.bcbf_pendulum_control_step_f64
 
     def step(ev_start=None, ev_stop=None):
@@ -1752,9 +1773,10 @@ def _pendulum_sampled_args(x, sampled):
     return (_p(z), _p(xdot_s), _p(cbc_s), _p(relaxed), _p(viol_relaxed), float(sampled.get("rho_tol", 1e-6)))
 
 
-def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled=None):
+def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled=None, nom=None):
     """The step of `pendulum_control_step_prepare` on bcbf_pendulum_control_step_observe_f64 (head: the plain entry's
-    arguments up to `fails`), or with `sampled` on bcbf_pendulum_control_step_sampled_f64."""
+    arguments up to `fails`), or with `sampled` on bcbf_pendulum_control_step_sampled_f64, or with `nom` (the LQR nominal
+    controller's numSteps, t, t_dev, lstatus) on bcbf_pendulum_control_step_nominal_f64."""
     if explore is not None and u_ref is not None:
         raise ValueError("explore wraps the greedy u_ref; it cannot be combined with a caller's u_ref")
     _chk(x, explore)
@@ -1763,28 +1785,69 @@ def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_
     what, draw = "bcbf_pendulum_control_step_observe", ()
     if sampled is not None:
         fn, what, draw = lib.bcbf_pendulum_control_step_sampled_f64, "bcbf_pendulum_control_step_sampled", _pendulum_sampled_args(x, sampled)
+    if nom is not None:
+        fn, what = lib.bcbf_pendulum_control_step_nominal_f64, "bcbf_pendulum_control_step_nominal"
+        draw = draw or (None, None, None, None, None, 1e-6)
     bound = dict(eps=float(eps), explore=explore)
-    keep = keep + (rng, explore, None if sampled is None else dict(sampled))
+    keep = keep + (rng, explore, None if sampled is None else dict(sampled), nom)
 
-    def step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None):
+    def step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None, t=None):
         ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
         ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
         ex = bound["explore"] if explore is None else explore
         if explore is not None:
             _chk(x, explore)
         o = (None, None, None, 1) if obs is None else (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
-        rc = fn(*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, *draw, Bt, 2, 1, ev0, ev1,
-                fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        lq = () if nom is None else (nom["code"], nom["numSteps"], nom["t"] if t is None else int(t), _p(nom["t_dev"]), _p(nom["lstatus"]))
+        rc = fn(*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, *draw, *lq, Bt, 2, 1, ev0,
+                ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         if rc:
             check(rc, what)
         return out
     step.keep = keep
+    step.lstatus = None if nom is None else nom["lstatus"]
     return step
 
 
 def pendulum_control_step(gp, ws, x, **kw):
     """One control step of the pendulum safety filter for a batch (see `pendulum_control_step_prepare`); returns ws['u']."""
     return pendulum_control_step_prepare(gp, ws, x, **kw)()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The reference's LQR nominal controller (bcbf_lqr_nominal_*: LQRController.control, controllers.py:64-115), batched.
+def lqr_nominal(Mk, Mj, x, x_goal, Q, R, dt, numSteps, t=0, t_dev=None, want_u0=False, out=None):
+    """LQRController.control for a batch: Mk[Bt,n,1+m] and Mj[Bt,n,(1+m)(1+n)] in the jets' layout (`posterior_jets`; g and the
+    x-Jacobians of f and g are read, f is not), x[Bt,n]; x_goal[n], Q[n,n], R[m,m] host values (sequences / CPU tensors).  Two
+    backward passes of T = max(numSteps - t, 1) iterations of the recursion of affine_backpropagation (ilqr.py:43-76), the second
+    linearised at the first's control; t_dev (an int32 device tensor [1]) replaces t and is read by the kernel, so a captured
+    graph can replay a shrinking horizon.  ctrl_range is not applied (the reference's LQR does not clip).
+    Returns (u[Bt,m], status[Bt]) or (u, u0, status) with want_u0; status 1 = some R + B'PB had a pivot that is not > 0 (u = u0 =
+    0 there).  out = (u, u0 | None, status) reuses the caller's buffers."""
+    _chk(x, Mk, Mj)
+    Bt, n = x.shape
+    m = Mk.shape[2] - 1 if Mk.dim() == 3 else -1
+    if x.dim() != 2 or tuple(Mk.shape) != (Bt, n, 1 + m) or tuple(Mj.shape) != (Bt, n, (1 + m) * (1 + n)):
+        raise ValueError("lqr_nominal: x %s must be [Bt,n], Mk %s [Bt,n,1+m] and Mj %s [Bt,n,(1+m)(1+n)]"
+                         % (tuple(x.shape), tuple(Mk.shape), tuple(Mj.shape)))
+    ct = ctypes.c_float if x.dtype == torch.float32 else ctypes.c_double
+    host = []
+    for name, v, size in (("x_goal", x_goal, n), ("Q", Q, n * n), ("R", R, m * m)):
+        flat = [float(e) for e in torch.as_tensor(v, dtype=torch.float64).reshape(-1).tolist()]
+        if len(flat) != size:
+            raise ValueError("lqr_nominal: %s must hold %d values, got %d" % (name, size, len(flat)))
+        host.append((ct * size)(*flat))
+    if t_dev is not None and (t_dev.dtype != torch.int32 or t_dev.device != x.device or t_dev.numel() < 1):
+        raise ValueError("lqr_nominal: t_dev is an int32 tensor on x's device")
+    if out is None:
+        out = (torch.empty(Bt, m, dtype=x.dtype, device=x.device),
+               torch.empty(Bt, m, dtype=x.dtype, device=x.device) if want_u0 else None,
+               torch.empty(Bt, dtype=torch.int32, device=x.device))
+    u, u0, status = out
+    _chk(x, u, u0, status)
+    check(getattr(lib, "bcbf_lqr_nominal" + _suf(x))(_p(Mk), _p(Mj), _p(x), *host, float(dt), int(numSteps), int(t), _p(t_dev),
+                                                    _p(u), _p(u0), _p(status), Bt, n, m, _stream(x)), "bcbf_lqr_nominal")
+    return (u, u0, status) if want_u0 else (u, status)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

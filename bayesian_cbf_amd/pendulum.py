@@ -427,10 +427,12 @@ class ControlPendulumCBFLearned:
                  iterations=100, dt=0.001, max_train=200, gamma_length_scale_prior=(math.pi / 100, math.pi / 100),
                  constraint_plotter_class=None, true_model=None, plotfile=None, dtype=torch.float64,
                  use_ground_truth_model=False, numSteps=1000, ctrl_range=(-15., 15.), u_quad_cost=((1.,),),
-                 enable_learning=False, model=None, exploration_controller_class=None, device=None):
+                 enable_learning=False, model=None, exploration_controller_class=None, device=None,
+                 unsafe_controller_class=None):
         """mean_dynamics_model_class None = partial(ZeroDynamicsModel, m=1, n=2), upstream's default.  model: the regressor
         (default a fresh ControlAffineRegressor(x_dim, u_dim, gamma_length_scale_prior=...) in `dtype`);
-        exploration_controller_class: default `EpsilonGreedyController` (tests pass a replaying subclass)."""
+        exploration_controller_class: default `EpsilonGreedyController` (tests pass a replaying subclass);
+        unsafe_controller_class: default `GreedyController`; `controllers.LQRController` is upstream's."""
         from .control_affine_model import ControlAffineRegressor
         from .controllers import ControlCBFLearned, EpsilonGreedyController, SOCPController
         from .unicycle_move_to_pose import ZeroDynamicsModel
@@ -450,7 +452,7 @@ class ControlPendulumCBFLearned:
             exploration_controller_class=exploration_controller_class or EpsilonGreedyController,
             egreedy_scheme=list(egreedy_scheme), enable_learning=enable_learning,
             mean_dynamics_model_class=mean_dynamics_model_class, max_train=max_train, controller_class=SOCPController,
-            training_iter=iterations)
+            training_iter=iterations, **({} if unsafe_controller_class is None else dict(unsafe_controller_class=unsafe_controller_class)))
         self.net_model = self.controller.net_model
 
     @property

@@ -1448,7 +1448,8 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
                              gp=None, shared=False, mean_model=None, true_model=(1.0, 10.0, 1.0), max_unsafe_prob=0.01,
                              k_alpha=(1.0, 3.0), cbf_col_theta=math.pi / 4, cbf_col_delta=math.pi / 8,
                              dtype=torch.float64, device="cuda", use_graph=False, record=False, seed=0, max_iters=100,
-                             hessian_mode="reference", plant="true", rho_tol=1e-6):
+                             hessian_mode="reference", plant="true", rho_tol=1e-6, nominal="greedy",
+                             lqr_numSteps=None):
     """Bt closed loops of the pendulum's rel-degree-2 safety filter (SOCPController with cbfs = [RadialCBFRelDegree2] and
     the greedy nominal controller, bcbf_pendulum_control_step) from perturbed start states, numSteps steps each.  The
     defaults are run_pendulum_control_online_learning's (pendulum.py:1041-1048: theta0 = 7 pi/12, tau = 0.002, 250 steps,
@@ -1474,10 +1475,19 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
     was never promised the risk); with record also cbc_s[numSteps,Bt,2] = (L_f h, CBC2) on the draw, status[numSteps,Bt] and
     rho[numSteps,Bt], the slack of every step.
     Draws of different steps are independent (the marginal at each visited (x_t, u_t) is exact); a trajectory is not one
-    function drawn from the GP."""
+    function drawn from the GP.
+
+    nominal: "greedy" (default) or "lqr" -- the reference's LQRController (its default for the learned pendulum controller,
+    controllers.py:64-115, 681) with the horizon numSteps - t at step t: eager passes the host t, use_graph a device step
+    counter the captured step increments.  The result gains lqr_failures, the number of instance-steps whose LQR recursion met
+    a non-positive pivot (`ops.lqr_nominal`'s status; the nominal control is 0 there).  lqr_numSteps: the controller's numSteps
+    when the loop runs fewer steps than the controller plans for (default: numSteps)."""
     if plant not in ("true", "posterior"):
         raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    if nominal not in ("greedy", "lqr"):
+        raise ValueError("nominal must be 'greedy' or 'lqr', got %r" % (nominal,))
     sampled = plant == "posterior"
+    lqr = nominal == "lqr"
     dev = torch.device(device)
     f = dict(dtype=dtype, device=dev)
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -1499,15 +1509,27 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
         cbc_traj = torch.empty(numSteps, Bt, 2, **f) if record else None
         status_traj = torch.empty(numSteps, Bt, dtype=torch.int32, device=dev) if record else None
         rho_traj = torch.empty(numSteps, Bt, **f) if record else None
+    nom = {}
+    if lqr:                # the horizon's step counter lives on the device under use_graph; lstatus failures accumulate per step
+        t_dev = torch.zeros(1, dtype=torch.int32, device=dev) if use_graph and not record else None
+        lfails = torch.zeros(Bt, dtype=torch.int32, device=dev)
+        state += [lfails] + ([t_dev] if t_dev is not None else [])
+        nom = dict(nominal="lqr", numSteps=numSteps if lqr_numSteps is None else lqr_numSteps, t_dev=t_dev)
     step = ops.pendulum_control_step_prepare(gp, ws, x, mean_model=mean_model, true_model=true_model, dt=dt,
                                              theta_c=cbf_col_theta, delta_c=cbf_col_delta, k_alpha=k_alpha,
                                              max_unsafe_prob=max_unsafe_prob, max_iters=max_iters,
-                                             hessian_mode=hessian_mode, stats=(min_h, fails), sampled=draw)
+                                             hessian_mode=hessian_mode, stats=(min_h, fails), sampled=draw, **nom)
 
     def one_step(t=None):
         if sampled:      # this step's draws (t: a python int, or the device counter inside the captured graph), then the risk counters
             draw["z"].copy_(z_all.index_select(0, t)[0] if torch.is_tensor(t) else z_all[t])
-        step()
+        if lqr:
+            step(t=None if t_dev is not None else t)
+            lfails.add_(step.lstatus)
+            if t_dev is not None:
+                t_dev.add_(1)
+        else:
+            step()
         if sampled:
             ops.rollout_risk(draw["cbc_s"], ws["status"], risk["viol"], risk["solved"], risk["min_cbc"])
 
@@ -1551,6 +1573,8 @@ def pendulum_safety_rollouts(Bt, numSteps=250, dt=0.002, theta0=7 * math.pi / 12
     out = dict(stats=stats, x_final=x, min_h=min_h, fails=fails, traj=traj, u=us, loop_seconds=t_loop, ws=ws)
     if sampled:
         out.update(risk=_pendulum_risk_result(draw, risk, max_unsafe_prob), cbc_s=cbc_traj, status=status_traj, rho=rho_traj)
+    if lqr:
+        out["lqr_failures"] = int(lfails.sum())
     return out
 
 
@@ -1587,7 +1611,7 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
                                start_noise=0.05, true_model=(1.0, 10.0, 1.0), max_unsafe_prob=0.01, k_alpha=(1.0, 3.0),
                                cbf_col_theta=math.pi / 4, cbf_col_delta=math.pi / 8, fit_lr=0.1,
                                gamma_length_scale_prior=(math.pi / 100, math.pi / 100), max_iters=100,
-                               hessian_mode="reference", device="cuda", plant="true", rho_tol=1e-6):
+                               hessian_mode="reference", device="cuda", plant="true", rho_tol=1e-6, nominal="greedy"):
     """Bt closed loops of the pendulum that LEARN their dynamics while the safety filter drives them
     (ControlPendulumCBFLearned, pendulum.py:909-961, through ControlCBFLearned / MeanAdjustedModel, controllers.py:320-378,
     665-736; the settings of run_pendulum_control_online_learning, pendulum.py:1041-1048), fp64, regime I: every instance
@@ -1623,13 +1647,18 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
     plant="posterior" (as `pendulum_safety_rollouts`): every step's plant is a draw from the model the instance holds at that
     step -- the prior until the first refit -- so the rows the loop learns from record the drawn plant; z_all[T,Bt,2,4] is drawn
     after explore (and is not part of `draws`); the result gains `risk`, with record also cbc_s[T,Bt,2].
+    nominal="lqr" (as `pendulum_safety_rollouts`): the explorer wraps the reference's LQRController -- upstream's default for this
+    class -- instead of the greedy control, horizon numSteps - t at step t; the result gains lqr_failures.
     Returns dict(stats (`reduce_rollout_stats`), report, x_final, min_h, fails; record: traj[T+1,Bt,2], u[T,Bt],
     u_ref[T,Bt], status[T,Bt], draws, rows = the stream buffers (X, UH, Y [Bt,T,2]), final = dict(X, UH, Y, jitter [Bt,N,.]
     of the last refit, hyper, gp = the model the loop ended with))."""
     from .controllers import epsilon
     if plant not in ("true", "posterior"):
         raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    if nominal not in ("greedy", "lqr"):
+        raise ValueError("nominal must be 'greedy' or 'lqr', got %r" % (nominal,))
     sampled = plant == "posterior"
+    lqr = nominal == "lqr"
     dev = torch.device(device)
     f = dict(dtype=torch.float64, device=dev)
     n, C = 2, 2
@@ -1687,6 +1716,9 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
         z_all = torch.randn(numSteps, Bt, 2, 4, generator=gen, **f)
         draw, risk = _pendulum_risk_buffers(Bt, rho_tol, f)
         kw["sampled"] = draw
+    if lqr:
+        lstatus, lfails = (torch.zeros(Bt, dtype=torch.int32, device=dev) for _ in range(2))
+        kw.update(nominal="lqr", numSteps=numSteps, lstatus=lstatus)
     ex = explore[0] if egreedy is not None else None          # (each call passes its step's [Bt,2] slice)
     step = ops.pendulum_control_step_prepare(dict(hyper), ws, x, prior=True, explore=ex, **kw)
     model = None
@@ -1707,7 +1739,10 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
         eps = epsilon(t, interpolate={0: egreedy[0], numSteps: egreedy[1]}) if egreedy is not None else 0.0
         if sampled:
             draw["z"].copy_(z_all[t])
-        step(eps=eps, explore=explore[t] if ex is not None else None, obs=(Xall[:, t], UHall[:, t], Yall[:, t], numSteps))
+        step(eps=eps, explore=explore[t] if ex is not None else None, obs=(Xall[:, t], UHall[:, t], Yall[:, t], numSteps),
+             **(dict(t=t) if lqr else {}))
+        if lqr:
+            lfails.add_(lstatus)
         if sampled:
             ops.rollout_risk(draw["cbc_s"], ws["status"], risk["viol"], risk["solved"], risk["min_cbc"])
             if record:
@@ -1783,6 +1818,8 @@ def pendulum_learning_rollouts(Bt, numSteps=250, dt=0.002, train_every=10, max_t
     out = dict(stats=stats, report=report, x_final=x, min_h=min_h, fails=fails, ws=ws)
     if sampled:
         out["risk"] = _pendulum_risk_result(draw, risk, max_unsafe_prob)
+    if lqr:
+        out["lqr_failures"] = int(lfails.sum())
     if record:
         out.update(rec)
         out["draws"] = dict(explore=explore, refits=refit_draws)

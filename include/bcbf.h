@@ -1146,6 +1146,61 @@ int bcbf_pendulum_control_step_sampled_f64(
     int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
     int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
 
+/* ---- The reference's LQR nominal controller (LQRController.control, controllers.py:64-115: the default
+ * unsafe_controller_class of ControlCBFLearned, controllers.py:681), batched: one lane per instance, the finite-horizon
+ * recursion in registers, 64-thread workgroups.  It replaces the reference's two `bdlqr.lqr.LinearSystem(...).solve(x, 1)`
+ * calls (controllers.py:87-97, 103-113) and the autograd Jacobians in front of them (controllers.py:77-79, 99-102).  `bdlqr`
+ * is an external package; the semantic here is the same author's in-tree statement of its recursion,
+ * affine_backpropagation (ilqr.py:43-76), cost u'Ru + 2 z'u + x'Qx + 2 s'x.  Parity with bdlqr's own iterates is not claimed.
+ * Inputs in the layout bcbf_posterior_jets* writes (C = 1+m, CT = C (1+n)):  g = Mk[b,:,1:],  Jf[i][d] = Mj[b,i,(1+d)C],
+ * Jg_j[i][d] = Mj[b,i,(1+d)C+1+j];  f = Mk[b,:,0] is not read.  Per instance, following the reference's code:
+ *     B = g dt,  s = -Q x_goal,  z = 0,  Q_T = Q,  s_T = s
+ *     pass(A): P = Q, o = s, then T times  G = R + B'PB,  K = G^-1 B'PA,  k = G^-1 (z + B'o),
+ *              P <- Q + A'PA - A'PB K,  o <- s + A'o - K'(z + B'o)  (K, k from the old P, o);  result -K x - k of the last
+ *              iteration, x the state itself (not x - x_goal)
+ *     u0 = pass(I + dt Jf),   u = pass(I + dt (Jf + sum_j Jg_j u0_j));   ctrl_range is not applied (the reference's LQR does not
+ *     clip; its epsilon-greedy wrapper does).
+ * Horizon T = max(numSteps - t, 1), t the host value or, when t_dev != NULL, the device int t_dev[0] read by the kernel (held
+ * to >= 0) -- a captured graph replays a shrinking horizon by incrementing that counter.  The clamp to 1 is this library's
+ * definition: the reference is undefined at t >= numSteps.
+ * x_goal[n], Q[n,n], R[m,m] (row-major): HOST values, passed to the kernel by value.  Device: Mk[Bt,n,C], Mj[Bt,n,CT], x[Bt,n]
+ * -> u[Bt,m], u0[Bt,m] (the first pass's control; may be NULL), status[Bt]: 0, or 1 where some G had a pivot that is not > 0 in
+ * the elimination without exchanges -- then u = u0 = 0 for that instance; other instances are unaffected.
+ * Every (1 <= n <= 4, 1 <= m <= 3).  The f32 entry reads and writes fp32 and carries P, o, K, k in fp64, as the f64 entry does.
+ * BCBF_EINVAL with a reason, before any HIP call, for: Bt < 0, n or m out of range, a null required pointer, dt <= 0 or NaN,
+ * numSteps < 1, t < 0 with t_dev == NULL. */
+int bcbf_lqr_nominal_f32(const float* Mk, const float* Mj, const float* x, const float* x_goal, const float* Q, const float* R,
+                         float dt, int numSteps, int t, const int* t_dev, float* u, float* u0, int* status, int Bt, int n,
+                         int m, void* stream);
+int bcbf_lqr_nominal_f64(const double* Mk, const double* Mj, const double* x, const double* x_goal, const double* Q,
+                         const double* R, double dt, int numSteps, int t, const int* t_dev, double* u, double* u0, int* status,
+                         int Bt, int n, int m, void* stream);
+
+/* The pendulum step with a choice of nominal controller.  Every argument of bcbf_pendulum_control_step_sampled_f64, plus
+ *   nominal (0: GreedyController, as the three entries above; 1: LQRController, the reference's default for
+ *     ControlPendulumCBFLearned), numSteps, t, t_dev (the horizon, as bcbf_lqr_nominal_f64), lstatus[Bt] (required with
+ *     nominal = 1: bcbf_lqr_nominal_f64's status; an instance with lstatus 1 has the nominal control 0 before explore / clip).
+ * z == NULL runs the observing entry's true plant, z != NULL the sampled entry's posterior-drawn plant.
+ * nominal = 1: after the task kernel has added the mean model to Mk / Mj, u_ref = bcbf_lqr_nominal_f64's u on those factors
+ * (x_goal, Q_goal, R, dt of this call; the same kernel), then the epsilon-greedy draw and the clip exactly as in the observing
+ * entry -- LQR, explore, clip -- and everything downstream is unchanged.  nominal = 0: bit for bit the observing / sampled entry.
+ * BCBF_EINVAL for every refusal of those entries and: nominal not 0 / 1; with nominal = 1: u_ref_in != NULL, lstatus == NULL,
+ * numSteps < 1, t < 0 with t_dev == NULL. */
+int bcbf_pendulum_control_step_nominal_f64(
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
+    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
+    int mean_model, double mean_mass, double mean_gravity, double mean_length,
+    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
+    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
+    double true_mass, double true_gravity, double true_length, double dt,
+    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
+    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
+    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
+    int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
+    int nominal, int numSteps, int t, const int* t_dev, int* lstatus,
+    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream);
+
 /* ---- The pendulum's CLF-CBF quadratic program on the KNOWN model (PendulumCBFCLFDirect, run_pendulum_control_cbf_clf:
  * pendulum.py:530-640, 770-906, 1019-1024).  Two rows, affine in the control, on the controller's model (m, g, l) at
  * x = (theta, omega), d = theta - theta_c:

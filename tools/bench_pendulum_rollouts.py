@@ -5,7 +5,10 @@ queried by every instance) at Bt = 4096 and 32768, regime I (one model per insta
 configuration: instance-steps/s of the eager loop (one host call per step) and of the HIP-graph replay, and the share of
 the step the jets launch takes (events around it, eager loop).
 --plant posterior: the same loops on plants drawn from the model's own posterior (bcbf_pendulum_control_step_sampled_f64); each
-line then carries the step time next to the true-plant loop's and the empirical risk of the drawn rel-degree-2 condition."""
+line then carries the step time next to the true-plant loop's and the empirical risk of the drawn rel-degree-2 condition.
+--nominal lqr [--lqr-numsteps K]: the same loops with the reference's LQRController as the nominal controller
+(bcbf_pendulum_control_step_nominal_f64), alternated with the greedy loop; each line carries both step times and the LQR
+kernel's own time at the full horizon (events around bcbf_lqr_nominal_f64 on the step's factors)."""
 import json
 import math
 import os
@@ -82,11 +85,66 @@ def posterior_line(regime, Bt, N, steps, kw, repeats=3):
     return line
 
 
-def main(configs=(("S", 4096), ("S", 32768), ("I", 4096)), plant="true"):
+def lqr_kernel_ms(gp, Bt, numSteps, launches=20):
+    """Milliseconds per launch of bcbf_lqr_nominal_f64 on the factors one step leaves, at the horizon numSteps (events)."""
+    x = torch.zeros(Bt, 2, dtype=torch.float64, device="cuda")
+    x[:, 0] = 7 * math.pi / 12
+    x0 = x.clone()
+    ws = ops.pendulum_workspace(Bt, torch.float64, "cuda")
+    ops.pendulum_control_step_prepare(gp, ws, x)()
+    out = (torch.empty(Bt, 1, dtype=torch.float64, device="cuda"), None, torch.empty(Bt, dtype=torch.int32, device="cuda"))
+    call = lambda: ops.lqr_nominal(ws["Mk"], ws["Mj"], x0, (0.0, 0.0), ((1.0, 0.0), (0.0, 1.0)), ((1.0,),), 0.002, numSteps, out=out)
+    for _ in range(3):
+        call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(launches):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / launches
+
+
+def nominal_line(regime, Bt, N, steps, kw, lqr_numSteps, repeats=3):
+    """One JSON line: the loop with the LQR nominal controller against the greedy loop, alternated `repeats` times in this
+    process (medians, with every repeat beside them), eager and graph."""
+    lq = dict(nominal="lqr", lqr_numSteps=lqr_numSteps)
+    for extra in ({}, lq):
+        pendulum_safety_rollouts(Bt, **dict(kw, numSteps=20, **extra))         # warm-up (clocks, lazy loads)
+    ms = {(nom, how): [] for nom in ("greedy", "lqr") for how in ("eager", "graph")}
+    iters = {}                  # the cone solver's iteration counts at the last step: its launch time follows the slowest lane
+    for _ in range(repeats):
+        for nom, extra in (("greedy", {}), ("lqr", lq)):
+            eager = pendulum_safety_rollouts(Bt, **kw, **extra)
+            it = eager["ws"]["iters"].double()
+            iters[nom] = dict(mean=float(it.mean()), max=int(it.max()), u_ref_abs_max=float(eager["ws"]["u_ref"].abs().max()))
+            graph = pendulum_safety_rollouts(Bt, use_graph=True, **kw, **extra)
+            ms[nom, "eager"].append(eager["loop_seconds"] * 1e3 / steps)
+            ms[nom, "graph"].append(graph["loop_seconds"] * 1e3 / steps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    line = dict(regime=regime, Bt=Bt, N=N, dtype="float64", steps=steps, nominal="lqr", lqr_numSteps=lqr_numSteps, repeats=repeats,
+                eager_ms_per_step=med["lqr", "eager"], graph_ms_per_step=med["lqr", "graph"],
+                greedy_eager_ms_per_step=med["greedy", "eager"], greedy_graph_ms_per_step=med["greedy", "graph"],
+                graph_ms_added=med["lqr", "graph"] - med["greedy", "graph"],
+                lqr_kernel_ms_full_horizon=lqr_kernel_ms(kw["gp"], Bt, lqr_numSteps),
+                last_step_solver_iters=iters, all_ms_per_step={"%s_%s" % k: v for k, v in ms.items()}, lqr_failures=eager["lqr_failures"],
+                collisions=eager["stats"]["collisions"], instances_with_failed_programs=eager["stats"]["solver_failures"],
+                min_h=eager["stats"]["min_h"], graph_equals_eager=bool(torch.equal(eager["x_final"], graph["x_final"])))
+    print(json.dumps(line), flush=True)
+    return line
+
+
+def main(configs=(("S", 4096), ("S", 32768), ("I", 4096)), plant="true", nominal="greedy", lqr_numSteps=None):
     N, steps = 512, int(os.environ.get("BCBF_PEND_STEPS", "250"))
     for regime, Bt in configs:
         gp = model(1 if regime == "S" else Bt, N)
         kw = dict(numSteps=steps, gp=gp, shared=regime == "S")
+        if nominal == "lqr":
+            nominal_line(regime, Bt, N, steps, dict(kw, plant=plant), lqr_numSteps or steps)
+            del gp
+            torch.cuda.empty_cache()
+            continue
         if plant == "posterior":
             posterior_line(regime, Bt, N, steps, kw)
             del gp
@@ -113,6 +171,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--only", nargs="+", metavar="REGIME:BT", help="a subset of the configurations, e.g. S:4096 (profiling runs)")
     ap.add_argument("--plant", choices=("true", "posterior"), default="true")
+    ap.add_argument("--nominal", choices=("greedy", "lqr"), default="greedy")
+    ap.add_argument("--lqr-numsteps", type=int, default=None, help="the LQR controller's numSteps (default: the loop's steps)")
     args = ap.parse_args()
     only = [a.split(":") for a in args.only] if args.only else None
-    main(tuple((r, int(b)) for r, b in only) if only else ((("S", 4096), ("S", 32768), ("I", 4096))), plant=args.plant)
+    main(tuple((r, int(b)) for r, b in only) if only else ((("S", 4096), ("S", 32768), ("I", 4096))), plant=args.plant,
+         nominal=args.nominal, lqr_numSteps=args.lqr_numsteps)
