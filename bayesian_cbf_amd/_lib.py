@@ -32,6 +32,8 @@ _SIGS = {
     "bcbf_mll_grad_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bcbf_fit_param_count": (c_int, [c_int, c_int, c_int, c_int]),
     "bcbf_coneqp_f64": (c_int, [P, P, P, P, c_int, c_int, ctypes.POINTER(c_int), c_int, P, P, P, c_int, c_int, P]),
+    # (is_f64, Bt, N, cus, has_Kdense, has_Ldense, kernel_kind, form) -> out_plan[4]: a host function, no device call
+    "bcbf_refit_plan": (c_int, [c_int] * 8 + [ctypes.POINTER(c_int)]),
     "bcbf_pendulum_control_step_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
                                                ctypes.POINTER(c_double), c_double, P] + [c_double] * 3 + [c_int] * 2
                                        + [c_double] * 4 + [P] * 24 + [c_int] * 3 + [P] * 3),
@@ -66,6 +68,8 @@ _TSIGS = {
     "bcbf_posterior_query_matern52": [P] * 13 + [c_int, c_int, c_int, c_int, c_int, P],
     "bcbf_posterior_query_rbfm52": [P] * 13 + [c_int, c_int, c_int, c_int, c_int, P],
     "bcbf_refit": [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    # the general refit entry: (X .. jitter, Kdense, Lop, UHB, Ldense, prev_info, info, Bt, N, n, m, kernel_kind, form, stream)
+    "bcbf_refit_form": [P] * 12 + [c_int] * 6 + [P],
     "bcbf_refit_retry": [P] * 10 + [c_int, c_int, c_int, c_int, P],
     "bcbf_refit_retry_kind": [P] * 10 + [c_int, c_int, c_int, c_int, c_int, P],
     "bcbf_gram": [P, P, P, c_int, c_int, c_int, c_int, P],

@@ -12,13 +12,9 @@
 // The 32x32 diagonal tile goes through LDS once to wave 0, which factors and inverts it in registers.
 // fp32 MFMA runs at the fp32 vector rate on gfx950: the gain is operand traffic / instruction count
 // (2 loads + 1 MFMA per 2048 MACs instead of LDS broadcasts), not peak.
-#include "bcbf_common.h"
+#include "refit_forms.h"
 #include "diag_tile64.h"
-#include <stdlib.h>
 
-#ifndef BCBF_R32_WAVE_MIN_BATCH
-#define BCBF_R32_WAVE_MIN_BATCH 1024
-#endif
 namespace bcbf {
 
 // v(lane) + v(lane ^ 32) in every lane on the VALU (gfx950 v_permlane32_swap; a __shfl_xor is an LDS round trip)
@@ -340,114 +336,23 @@ refit_mfma_kernel(const float* __restrict__ X, const float* __restrict__ UH, con
     if (tid == 0) info[b] = fail;
 }
 
-int launch_refit_wave32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                        const float* jitter, const float* Kdense, float* Lop, float* UHB, float* Ldense, int* info,
-                        int Bt, int N, int Np, int n, int C, hipStream_t st);          // refit_wave64.hip
-int launch_refit_pair32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                        const float* jitter, float* Lop, float* UHB, int* info, int Bt, int N, int Np, int n, int C,
-                        hipStream_t st);                                               // refit_wave64.hip: two waves per instance
-
-
-int launch_refit_slab32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                        const float* jitter, float* Lop, float* UHB, int* info, int Bt, int N, int Np, int n, int C,
-                        hipStream_t st);                                               // refit_slab.hip: four waves per instance, operands staged through LDS
-int launch_refit_team32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                        const float* jitter, const float* Kdense, float* Lop, float* UHB, float* Ldense, int* info, int Bt, int N,
-                        int Np, int n, int C, int nw, hipStream_t st);                 // refit_wave64.hip: a team of eight (four) waves per instance
-
-}  // namespace bcbf
-
-extern "C" int bcbf_refit_mfma_f32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                                   const float* jitter, const float* Kdense, float* Lop, float* UHB, float* Ldense,
-                                   int* info, int Bt, int N, int n, int m, void* stream) {
-    using namespace bcbf;
-    if (Bt <= 0) return BCBF_OK;
-    if (!Lop || !info || N < 1) return BCBF_EINVAL;
-    const int Np = round_up(N, NB);
-    hipStream_t st = (hipStream_t)stream;
-    // Batches: one wave per instance (refit_wave64.hip, also compiled for fp32); BCBF_REFIT_WAVE=0/1 forces a form
-    bool per_wave = Bt >= BCBF_R32_WAVE_MIN_BATCH || (Bt >= 256 && Np <= 1024) || (Bt >= 128 && Np <= 512) || (Bt >= 64 && Np <= 128);
-    if (const char* e = getenv("BCBF_REFIT_WAVE")) per_wave = e[0] == '1';
-    // Two waves per instance (refit_wave64.hip): measured in fp32 (ms workgroup / wave / two waves): 1024 x 128: 0.172 /
-    // 0.070 / 0.058, 4096 x 128: 0.67 / 0.20 / 0.22, 1024 x 256: 0.441 / 0.220 / 0.186, 4096 x 256: 1.76 / 0.69 / 0.84,
-    // 256 x 512: 1.17 / 0.90 / 0.85, 512 x 512: 1.31 / 0.93 / 0.93, 1024 x 512: 1.69 / 1.04 / 1.18, 4096 x 512: 6.6 / 3.7 / 5.4,
-    // 64 x 512: 0.72 / 0.87 / 0.75, 256 x 1024: 5.5 / 5.3 / -
-    // (ONE model, tools/dev/time_refit_one.py, us workgroup / two waves / team: N = 128: 105 / 41 / 44, 256: 236 / 131 / 96, 512:
-    // 705 / 741 / 264, 1024: 2820 / - / 1311.)
-    bool pair = Bt <= 1024 && (Np <= 256 || (Np <= 512 && Bt >= 128 && Bt <= 256));
-    if (const char* e = getenv("BCBF_REFIT_PAIR")) pair = e[0] == '1' && Np / NB <= 16;
-    // A team of eight waves per instance (refit_wave64.hip: one chain wave, seven bulk waves; one workgroup per CU at a
-    // time) while ONE round of workgroups holds the batch, two rounds from N = 512 on, four from 1024 (1024 x 1024 fp32: 6.57 / 6.90)
-    // -- measured on 256 CUs
-    // (tools/dev/check_refit_team.py, ms team / best other form), fp32: 1 x 512: 0.27 / 0.71, 256 x 512: 0.30 / 0.86, 512 x 512:
-    // 0.61 / 0.93, 1024 x 512: 1.22 / 1.04, 1 x 1024: 1.31 / 2.81, 512 x 1024: 3.32 / 5.89, 256 x 256: 0.108 / 0.140,
-    // 512 x 256: 0.21 / 0.16, 256 x 128: 0.047 / 0.045; fp64: 1 x 512: 0.43 / 0.90, 256 x 512: 0.52 / 1.12, 512 x 512:
-    // 1.04 / 1.55, 1 x 1024: 2.31 / 3.57, 1 x 2048: 16.8 / 19.3, 256 x 256: 0.173 / 0.219.  BCBF_REFIT_TEAM=0/1 forces the
-    // choice (N <= 8192)
-    static int cus_ = 0;
-    if (cus_ == 0) {
-        int dev_ = 0, c_ = 256;
-        (void)hipGetDevice(&dev_);
-        (void)hipDeviceGetAttribute(&c_, hipDeviceAttributeMultiprocessorCount, dev_);
-        cus_ = c_ > 0 ? c_ : 256;
-    }
-    bool team = Np / NB <= 64 &&       // (N <= 2048: beyond, no better than the workgroup form -- 1 x 4096 fp64: 128 / 125 ms)
-                ((Np >= 256 && Bt <= cus_) || (Np >= 512 && Bt <= 2 * cus_) || (Np >= 1024 && Bt <= ((Kdense || Ldense) ? 4 : 2) * cus_));   // (1024 x 1024 fp32: team 6.67, one wave with super-panels 5.29 ms)
-    // ... of four waves (two workgroups per CU) for cus < batch <= 2 cus at 256 <= N <= 512: 512 x 256 fp64 0.259 (two waves per
-    // instance) / 0.210, fp32 0.162 / 0.136; 512 x 512 fp32 0.62 (team of eight, two rounds) / 0.53
-    int team_nw = 8;
-    if (Np / NB <= 16 && Np >= 256 && Bt > cus_ && Bt <= 2 * cus_ && !Kdense) { team = true; team_nw = 4; }
-    if (getenv("BCBF_REFIT_WAVE") || getenv("BCBF_REFIT_PAIR")) team = false;      // (another form is being forced)
-    if (const char* e = getenv("BCBF_REFIT_TEAM")) { team = e[0] == '1' && Np / NB <= 256; if (e[0] == '1' && e[1] == '4') team_nw = 4; else if (e[0] == '1' && e[1] == '8') team_nw = 8; }
-    // Large batches of N = 384 .. 512 (refit_slab.hip): BCBF_REFIT_SLAB=0/1 forces the choice
-    bool slab = false;
-    if (const char* e = getenv("BCBF_REFIT_SLAB")) slab = e[0] == '1';
-    if (slab && !Kdense && !Ldense) {
-        if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-        if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-        if (launch_refit_slab32(X, UH, Bm, ell, s2, jitter, Lop, UHB, info, Bt, N, Np, n, m + 1, st) == 0) return check_launch("refit_slab32");
-    }
-    if (team) {
-        if (!Kdense) {
-            if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-            if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-        }
-        if (launch_refit_team32(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, m + 1, team_nw, st) != 0) return BCBF_EINVAL;       // a size the form does not address
-        return check_launch("refit_team32");
-    }
-    if (pair && !Kdense && !Ldense) {
-        if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-        if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-        if (launch_refit_pair32(X, UH, Bm, ell, s2, jitter, Lop, UHB, info, Bt, N, Np, n, m + 1, st) != 0) return BCBF_EINVAL;       // a size the form does not address
-        return check_launch("refit_pair32");
-    }
-    if (per_wave) {
-        if (!Kdense) {
-            if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-            if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-        }
-        launch_refit_wave32(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, m + 1, st);
-        return check_launch("refit_wave32");
-    }
-    // few instances: 8 waves per workgroup with the 4-column-blocked diagonal tile (256-register budget) beat 16 waves with
-    // the unrolled 32-step tile (128 registers: the blocked routine spills there) -- ONE model, fp32: 126 -> 107 us at N = 128,
-    // 288 -> 235 at 256, 754 -> 702 at 512, 2991 -> 2815 at 1024.  BCBF_REFIT_WIDE8=0 keeps the 16-wave form
-    static const int wide8 = [] { const char* e = getenv("BCBF_REFIT_WIDE8"); return e ? atoi(e) : 1; }();
-    const bool wide = Bt < 128 && N >= 128;   // few instances: 16 waves per workgroup and the unrolled diagonal-tile code (Bt=1: 145 -> 117 us at N=128, 346 -> 273 at 256, 869 -> 725 at 512, 2115 -> 1990 at 1024)
+// The workgroup form, fp32 (refit.hip: choose_refit_plan picks plan.waves).  Few instances: 8 waves per workgroup with the
+// 4-column-blocked diagonal tile (256-register budget); batches: 4 waves, several workgroups per CU.
+template <>
+int launch_refit_workgroup<float>(const RefitArgs<float>& a, const RefitPlan& plan) {
 #define BCBF_REFIT_LAUNCH(DENSE, ...)                                                                   \
     do {                                                                                                \
-        if (wide && wide8) hipLaunchKernelGGL((refit_mfma_kernel<DENSE, 8>), dim3(Bt), dim3(512), __VA_ARGS__);       \
-        else if (wide) hipLaunchKernelGGL((refit_mfma_kernel<DENSE, 16>), dim3(Bt), dim3(1024), __VA_ARGS__);         \
-        else hipLaunchKernelGGL((refit_mfma_kernel<DENSE, 4>), dim3(Bt), dim3(256), __VA_ARGS__);                     \
+        if (plan.waves == 8) hipLaunchKernelGGL((refit_mfma_kernel<DENSE, 8>), dim3(a.Bt), dim3(512), __VA_ARGS__);   \
+        else hipLaunchKernelGGL((refit_mfma_kernel<DENSE, 4>), dim3(a.Bt), dim3(256), __VA_ARGS__);                   \
     } while (0)
-    if (Kdense) {
-        BCBF_REFIT_LAUNCH(true, 0, st, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, Kdense, Lop, nullptr, Ldense, info, N, Np, 0, 0, g_refit_only_bad);
-    } else {
-        if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-        if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-        BCBF_REFIT_LAUNCH(false, 0, st, X, UH, Bm, ell, s2, jitter, nullptr,
-                           Lop, UHB, Ldense, info, N, Np, n, m + 1, g_refit_only_bad);
-    }
-    return check_launch("refit_mfma");
+    if (a.Kdense)
+        BCBF_REFIT_LAUNCH(true, 0, a.stream, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, a.Kdense, a.Lop, nullptr, a.Ldense, a.info, a.N, a.Np, 0, 0, a.only_bad);
+    else
+        BCBF_REFIT_LAUNCH(false, 0, a.stream, a.X, a.UH, a.Bm, a.ell, a.s2, a.jitter, nullptr,
+                           a.Lop, a.UHB, a.Ldense, a.info, a.N, a.Np, a.n, a.C, a.only_bad);
+#undef BCBF_REFIT_LAUNCH
+    return 0;
 }
+
+}  // namespace bcbf

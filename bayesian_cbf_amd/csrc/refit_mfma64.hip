@@ -12,8 +12,7 @@
 // Wave 0 factors and inverts the 32x32 diagonal tile in registers (lane = row, v_readlane broadcasts) while waves 1-3
 // run their update streams.  fp64 MFMA peak on MI355X is 78.6 TFLOP/s = the fp64 vector peak; as in fp32 the gain over
 // the VALU kernel is operand traffic and instruction count.
-#include "bcbf_common.h"
-#include <stdlib.h>
+#include "refit_forms.h"
 
 namespace bcbf {
 
@@ -333,102 +332,25 @@ refit_mfma64_kernel(const double* __restrict__ X, const double* __restrict__ UH,
     if (tid == 0) info[b] = fail;
 }
 
-int launch_refit_wave64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
-                        const double* jitter, const double* Kdense, double* Lop, double* UHB, double* Ldense, int* info,
-                        int Bt, int N, int Np, int n, int C, hipStream_t st);          // refit_wave64.hip
-int launch_refit_pair64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
-                        const double* jitter, double* Lop, double* UHB, int* info, int Bt, int N, int Np, int n, int C,
-                        hipStream_t st);                                               // refit_wave64.hip: two waves per instance
-
-
-int launch_refit_team64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
-                        const double* jitter, const double* Kdense, double* Lop, double* UHB, double* Ldense, int* info, int Bt, int N,
-                        int Np, int n, int C, int nw, hipStream_t st);                 // refit_wave64.hip: a team of eight (four) waves per instance
-
-}  // namespace bcbf
-
-extern "C" int bcbf_refit_mfma_f64(const double* X, const double* UH, const double* Bm, const double* ell,
-                                   const double* s2, const double* jitter, const double* Kdense, double* Lop,
-                                   double* UHB, double* Ldense, int* info, int Bt, int N, int n, int m, void* stream) {
-    using namespace bcbf;
-    if (Bt <= 0) return BCBF_OK;
-    if (!Lop || !info || N < 1) return BCBF_EINVAL;
-    const int Np = round_up(N, NB);
-    hipStream_t st = (hipStream_t)stream;
-    if (!Kdense) {
-        if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-        if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-    }
-    // Batches: one wave per instance (refit_wave64.hip) -- every SIMD advances its own factorisation chain.
-    // Measured (tools/bench_refit_forms.py, MI355X): the per-wave form wins from 1024 instances on at every N (N = 256:
-    // 0.45 vs 0.82 ms at 1024, 1.75 vs 3.2 ms at 4096; N = 512: 2.1 vs 3.1 and 8.2 vs 12.0; N = 1024: 15.0 vs 15.7),
-    // from 512 at N <= 256 and from 64 at N <= 128; below that the workgroup form, whose four waves share one
-    // instance's update stream.  (The 4-column-blocked diagonal tile of the per-wave form was also tried here for wave 0:
-    // it needs ~100 more registers than this kernel's 256 budget leaves, spills, and is 7 % slower than the 32-step
-    // form below.)
-    bool per_wave = Bt >= 1024 || (Bt >= 512 && Np <= 512) || (Bt >= 64 && Np <= 128);
-    if (const char* e = getenv("BCBF_REFIT_WAVE")) per_wave = e[0] == '1';
-    // Two waves per instance (refit_wave64.hip, round 3: the serial chain of diagonal tiles on one wave, every other tile on
-    // the other) wins for small systems while one round of workgroups holds the batch -- measured (tools/bench_refit_forms.py,
-    // ms workgroup / wave / two waves): 1024 x 256: 0.822 / 0.357 / 0.328, 64 x 256: 0.303 / 0.311 / 0.204, 1024 x 128: 0.319 /
-    // 0.104 / 0.100, 64 x 128: 0.132 / 0.093 / 0.066; a tie at 4096 (x 256: 3.24 / 1.367 / 1.390) -- and loses at N = 512
-    // (256 x 512: 1.12 / 1.50 / 1.40, 1024 x 512: 3.06 / 1.88 / 2.26), where the one-wave form (512 registers) keeps more of the
-    // update stream in flight.  BCBF_REFIT_PAIR=0/1 forces the choice (N <= 512).
-    // (ONE model, tools/dev/time_refit_one.py, us workgroup / two waves / team: N = 128: 133 / 61 / 65, 256: 308 / 199 / 147, 512:
-    // 901 / 1193 / 423, 1024: 3565 / - / 2311.)
-    bool pair = Bt <= 1024 && Np <= 256;
-    if (const char* e = getenv("BCBF_REFIT_PAIR")) pair = e[0] == '1' && Np / NB <= 16;
-    // A team of eight waves per instance (refit_wave64.hip: one chain wave, seven bulk waves; one workgroup per CU at a
-    // time) while ONE round of workgroups holds the batch, two rounds from N = 512 on, four from 1024 (1024 x 1024 fp32: 6.57 / 6.90)
-    // -- measured on 256 CUs
-    // (tools/dev/check_refit_team.py, ms team / best other form), fp32: 1 x 512: 0.27 / 0.71, 256 x 512: 0.30 / 0.86, 512 x 512:
-    // 0.61 / 0.93, 1024 x 512: 1.22 / 1.04, 1 x 1024: 1.31 / 2.81, 512 x 1024: 3.32 / 5.89, 256 x 256: 0.108 / 0.140,
-    // 512 x 256: 0.21 / 0.16, 256 x 128: 0.047 / 0.045; fp64: 1 x 512: 0.43 / 0.90, 256 x 512: 0.52 / 1.12, 512 x 512:
-    // 1.04 / 1.55, 1 x 1024: 2.31 / 3.57, 1 x 2048: 16.8 / 19.3, 256 x 256: 0.173 / 0.219.  BCBF_REFIT_TEAM=0/1 forces the
-    // choice (N <= 8192)
-    static int cus_ = 0;
-    if (cus_ == 0) {
-        int dev_ = 0, c_ = 256;
-        (void)hipGetDevice(&dev_);
-        (void)hipDeviceGetAttribute(&c_, hipDeviceAttributeMultiprocessorCount, dev_);
-        cus_ = c_ > 0 ? c_ : 256;
-    }
-    bool team = Np / NB <= 64 &&       // (N <= 2048: beyond, no better than the workgroup form -- 1 x 4096 fp64: 128 / 125 ms)
-                ((Np >= 256 && Bt <= cus_) || (Np >= 512 && Bt <= 2 * cus_) || (Np >= 1024 && Bt <= ((Kdense || Ldense) ? 4 : 2) * cus_));   // (1024 x 1024 fp64: team 13.2, one wave with super-panels 12.8 ms)
-    // ... of four waves (two workgroups per CU) for cus < batch <= 2 cus at 256 <= N <= 512: 512 x 256 fp64 0.259 (two waves per
-    // instance) / 0.210, fp32 0.162 / 0.136; 512 x 512 fp32 0.62 (team of eight, two rounds) / 0.53
-    int team_nw = 8;
-    if (Np / NB <= 16 && Np >= 256 && Bt > cus_ && Bt <= 2 * cus_ && !Kdense) { team = true; team_nw = 4; }
-    if (getenv("BCBF_REFIT_WAVE") || getenv("BCBF_REFIT_PAIR")) team = false;      // (another form is being forced)
-    if (const char* e = getenv("BCBF_REFIT_TEAM")) { team = e[0] == '1' && Np / NB <= 256; if (e[0] == '1' && e[1] == '4') team_nw = 4; else if (e[0] == '1' && e[1] == '8') team_nw = 8; }
-    if (team) {
-        if (!Kdense) {
-            if (!X || !UH || !Bm || !ell || !s2 || !UHB) return BCBF_EINVAL;
-            if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;
-        }
-        if (launch_refit_team64(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, m + 1, team_nw, st) != 0) return BCBF_EINVAL;       // a size the form does not address
-        return check_launch("refit_team64");
-    }
-    if (pair && !Kdense && !Ldense) {
-        if (launch_refit_pair64(X, UH, Bm, ell, s2, jitter, Lop, UHB, info, Bt, N, Np, n, m + 1, st) != 0) return BCBF_EINVAL;       // a size the form does not address
-        return check_launch("refit_pair64");
-    }
-    if (per_wave) {
-        launch_refit_wave64(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, m + 1, st);
-        return check_launch("refit_wave64");
-    }
-    const bool wide = Bt < 128 && N >= 256;  // few large instances: 8 waves per workgroup (16 would cap the VGPRs at 128: spills)
+// The workgroup form, fp64 (refit.hip: choose_refit_plan picks plan.waves).  Few large instances: 8 waves per workgroup (16
+// would cap the VGPRs at 128: spills); otherwise 4, whose waves share one instance's update stream.  (The 4-column-blocked
+// diagonal tile of the one-wave form was also tried here for wave 0: it needs ~100 more registers than this kernel's 256
+// budget leaves, spills, and is 7 % slower than the 32-step form above.)
+template <>
+int launch_refit_workgroup<double>(const RefitArgs<double>& a, const RefitPlan& plan) {
 #define BCBF_REFIT_LAUNCH(DENSE, ...)                                                                   \
     do {                                                                                                \
-        if (wide) hipLaunchKernelGGL((refit_mfma64_kernel<DENSE, 8>), dim3(Bt), dim3(512), __VA_ARGS__);                \
-        else hipLaunchKernelGGL((refit_mfma64_kernel<DENSE, 4>), dim3(Bt), dim3(256), __VA_ARGS__);                     \
+        if (plan.waves == 8) hipLaunchKernelGGL((refit_mfma64_kernel<DENSE, 8>), dim3(a.Bt), dim3(512), __VA_ARGS__);   \
+        else hipLaunchKernelGGL((refit_mfma64_kernel<DENSE, 4>), dim3(a.Bt), dim3(256), __VA_ARGS__);                   \
     } while (0)
-    if (Kdense) {
-        BCBF_REFIT_LAUNCH(true, 0, st, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, Kdense, Lop, nullptr, Ldense, info, N, Np, 0, 0, g_refit_only_bad);
-    } else {
-        BCBF_REFIT_LAUNCH(false, 0, st, X, UH, Bm, ell, s2, jitter, nullptr,
-                           Lop, UHB, Ldense, info, N, Np, n, m + 1, g_refit_only_bad);
-    }
-    return check_launch("refit_mfma64");
+    if (a.Kdense)
+        BCBF_REFIT_LAUNCH(true, 0, a.stream, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, a.Kdense, a.Lop, nullptr, a.Ldense, a.info, a.N, a.Np, 0, 0, a.only_bad);
+    else
+        BCBF_REFIT_LAUNCH(false, 0, a.stream, a.X, a.UH, a.Bm, a.ell, a.s2, a.jitter, nullptr,
+                           a.Lop, a.UHB, a.Ldense, a.info, a.N, a.Np, a.n, a.C, a.only_bad);
+#undef BCBF_REFIT_LAUNCH
+    return 0;
 }
+
+}  // namespace bcbf

@@ -30,7 +30,7 @@
 // workgroup-form kernels, refit_mfma*.hip: they run four waves per SIMD against a 128 / 256-register cap, waits are
 // hidden by the other waves and the extra values in flight spill.)
 #include <type_traits>
-#include "bcbf_common.h"
+#include "refit_forms.h"
 #ifdef BCBF_RP_TRACE
 // time stamps inside the diagonal tile's factor + inverse (first call of workgroup 0 only), after the hand-off stamps
 namespace bcbf { __device__ long long rp_trace_buf[2][4096]; __device__ int dt_trace_n; }
@@ -1697,23 +1697,15 @@ refit_pair_kernel(const T* __restrict__ X, const T* __restrict__ UH, const T* __
 }
 
 template <typename T>
-static int launch_refit_pair(const T* X, const T* UH, const T* Bm, const T* ell, const T* s2, const T* jitter, T* Lop, T* UHB,
-                              int* info, int Bt, int N, int Np, int n, int C, hipStream_t st) {
-    if (Np / NB > RA_MAXBLK) return -1;
-    if ((unsigned long long)lop_elems<16 / (int)sizeof(T)>(Np) * sizeof(T) >= (1ull << 31)) return -1;    // 32-bit byte offsets
-    hipLaunchKernelGGL((refit_pair_kernel<T>), dim3(Bt), dim3(128), 0, st, X, UH, Bm, ell, s2, jitter, Lop, UHB, info, Bt, N, Np, n, C, g_refit_only_bad);
+int launch_refit_pair(const RefitArgs<T>& a, const RefitPlan&) {
+    if (a.Np / NB > RA_MAXBLK || a.Kdense || a.Ldense) return -1;
+    if ((unsigned long long)lop_elems<16 / (int)sizeof(T)>(a.Np) * sizeof(T) >= (1ull << 31)) return -1;    // 32-bit byte offsets
+    hipLaunchKernelGGL((refit_pair_kernel<T>), dim3(a.Bt), dim3(128), 0, a.stream, a.X, a.UH, a.Bm, a.ell, a.s2, a.jitter, a.Lop, a.UHB,
+                       a.info, a.Bt, a.N, a.Np, a.n, a.C, a.only_bad);
     return 0;
 }
-int launch_refit_pair64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
-                         const double* jitter, double* Lop, double* UHB, int* info, int Bt, int N, int Np, int n, int C,
-                         hipStream_t st) {
-    return launch_refit_pair<double>(X, UH, Bm, ell, s2, jitter, Lop, UHB, info, Bt, N, Np, n, C, st);
-}
-int launch_refit_pair32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                         const float* jitter, float* Lop, float* UHB, int* info, int Bt, int N, int Np, int n, int C,
-                         hipStream_t st) {
-    return launch_refit_pair<float>(X, UH, Bm, ell, s2, jitter, Lop, UHB, info, Bt, N, Np, n, C, st);
-}
+template int launch_refit_pair<float>(const RefitArgs<float>&, const RefitPlan&);
+template int launch_refit_pair<double>(const RefitArgs<double>&, const RefitPlan&);
 
 // ----------------------------------------------------------------------------------------------------------------
 // FEW LARGE INSTANCES: A TEAM OF WAVES PER INSTANCE (round 3).  The two-wave kernel above with the bulk role on NW - 1
@@ -2148,140 +2140,62 @@ refit_team_kernel(const T* __restrict__ X, const T* __restrict__ UH, const T* __
     }
 }
 
+// plan.waves = 8: one workgroup per CU at a time; 4 (two workgroups per CU; never from a dense K_b).  a.kind != 0: the OPT-IN
+// Matern-5/2 / RBF x Matern-5/2 data kernels (the reference has no Matern kernel; BASELINE.json's north_star names one), whose
+// only form is the team of eight.
 template <typename T>
-static int launch_refit_team(const T* X, const T* UH, const T* Bm, const T* ell, const T* s2, const T* jitter, const T* Kdense,
-                             T* Lop, T* UHB, T* Ldense, int* info, int Bt, int N, int Np, int n, int C, int nw, hipStream_t st,
-                             int kind = 0) {
-    if (Np / NB > RT_MAXBLK) return -1;
-    if (kind != 0) {
-        if (Kdense || (unsigned long long)lop_elems<16 / (int)sizeof(T)>(Np) * sizeof(T) >= (1ull << 31)) return -1;
-        if (kind == 1)
-            hipLaunchKernelGGL((refit_team_kernel<T, 8, false, 1>), dim3(Bt), dim3(512), 0, st, X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, g_refit_only_bad);
-        else if (kind == 2)
-            hipLaunchKernelGGL((refit_team_kernel<T, 8, false, 2>), dim3(Bt), dim3(512), 0, st, X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, g_refit_only_bad);
-        else return -1;
-        return 0;
-    }
+int launch_refit_team(const RefitArgs<T>& a, const RefitPlan& plan) {
+    if (a.Np / NB > RT_MAXBLK) return -1;
     // the kernel addresses one instance's operator with 32-bit byte offsets (buffer resource size, scalar + lane offsets)
-    if ((unsigned long long)lop_elems<16 / (int)sizeof(T)>(Np) * sizeof(T) >= (1ull << 31)) return -1;
-    // four waves per instance (two workgroups per CU) when the batch needs more than one workgroup per CU but not more than
-    // two: 512 x 256 fp64 0.259 (two waves per instance) / 0.330 (team of eight, two rounds) / 0.210 ms
-    if (nw == 4 && !Kdense) {
-        hipLaunchKernelGGL((refit_team_kernel<T, 4, false>), dim3(Bt), dim3(256), 0, st, X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, g_refit_only_bad);
-        return 0;
+    if ((unsigned long long)lop_elems<16 / (int)sizeof(T)>(a.Np) * sizeof(T) >= (1ull << 31)) return -1;
+#define BCBF_RT_LAUNCH(NW_, ...)                                                                                              \
+    hipLaunchKernelGGL((refit_team_kernel<T, NW_, __VA_ARGS__>), dim3(a.Bt), dim3(64 * NW_), 0, a.stream, a.X, a.UH, a.Bm, a.ell, \
+                       a.s2, a.jitter, a.Kdense, a.Lop, a.UHB, a.Ldense, a.info, a.Bt, a.N, a.Np, a.n, a.C, a.only_bad)
+    if (a.kind != 0) {
+        if (a.Kdense) return -1;
+        if (a.kind == 1) BCBF_RT_LAUNCH(8, false, 1);
+        else if (a.kind == 2) BCBF_RT_LAUNCH(8, false, 2);
+        else return -1;
+    } else if (plan.waves == 4 && !a.Kdense) {
+        BCBF_RT_LAUNCH(4, false);
+    } else if (a.Kdense) {
+        BCBF_RT_LAUNCH(8, true);
+    } else {
+        BCBF_RT_LAUNCH(8, false);
     }
-    if (Kdense)
-        hipLaunchKernelGGL((refit_team_kernel<T, 8, true>), dim3(Bt), dim3(512), 0, st, X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, g_refit_only_bad);
-    else
-        hipLaunchKernelGGL((refit_team_kernel<T, 8, false>), dim3(Bt), dim3(512), 0, st, X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, g_refit_only_bad);
+#undef BCBF_RT_LAUNCH
     return 0;
 }
-int launch_refit_team64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
-                        const double* jitter, const double* Kdense, double* Lop, double* UHB, double* Ldense, int* info, int Bt, int N,
-                        int Np, int n, int C, int nw, hipStream_t st) {
-    return launch_refit_team<double>(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, nw, st);
-}
-}  // namespace bcbf
+template int launch_refit_team<float>(const RefitArgs<float>&, const RefitPlan&);
+template int launch_refit_team<double>(const RefitArgs<double>&, const RefitPlan&);
 
-// Fused K_b build + jittered Cholesky + packing with the OPT-IN Matern-5/2 data kernel (the reference has no Matern kernel;
-// BASELINE.json's north_star names one): arguments of bcbf_refit.  One form -- a team of eight waves per instance.
-#define BCBF_REFIT_MATERN(SUF, T, NAME, KINDV)                                                                              \
-    extern "C" int NAME##SUF(const T* X, const T* UH, const T* Bm, const T* ell, const T* s2, const T* jitter,                   \
-                                             T* Lop, T* UHB, T* Ldense, int* info, int Bt, int N, int n, int m, void* stream) { \
-        using namespace bcbf;                                                                                                \
-        if (Bt <= 0) return BCBF_OK;                                                                                         \
-        if (!X || !UH || !Bm || !ell || !s2 || !Lop || !UHB || !info || N < 1) return BCBF_EINVAL;                            \
-        if (n < 1 || n > BCBF_MAX_STATE_DIM || m < 1 || m > BCBF_MAX_CTRL_DIM) return BCBF_EINVAL;                            \
-        if (launch_refit_team<T>(X, UH, Bm, ell, s2, jitter, nullptr, Lop, UHB, Ldense, info, Bt, N, round_up(N, NB), n,      \
-                                 m + 1, 8, (hipStream_t)stream, KINDV) != 0)                                                 \
-            return BCBF_EINVAL;                                                                                              \
-        return check_launch("refit_matern52");                                                                               \
-    }
-BCBF_REFIT_MATERN(f32, float, bcbf_refit_matern52_, 1)
-BCBF_REFIT_MATERN(f64, double, bcbf_refit_matern52_, 1)
-BCBF_REFIT_MATERN(f32, float, bcbf_refit_rbfm52_, 2)          // the product kernel RBF x Matern-5/2
-BCBF_REFIT_MATERN(f64, double, bcbf_refit_rbfm52_, 2)
-#undef BCBF_REFIT_MATERN
-// bcbf_refit_retry (refit.hip) for a state of any data kernel: kernel_kind 0 = RBF (bcbf_refit_retry itself), 1 = Matern-5/2,
-// 2 = RBF x Matern-5/2 -- only the instances with prev_info[b] != 0 are factored again, the others report 0
-extern "C" int bcbf_refit_mfma_f32(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
-                                   float*, float*, float*, int*, int, int, int, int, void*);
-extern "C" int bcbf_refit_mfma_f64(const double*, const double*, const double*, const double*, const double*, const double*,
-                                   const double*, double*, double*, double*, int*, int, int, int, int, void*);
-#define BCBF_REFIT_RETRY_KIND(SUF, T)                                                                                        \
-    extern "C" int bcbf_refit_retry_kind_##SUF(const T* X, const T* UH, const T* Bm, const T* ell, const T* s2,               \
-                                               const T* jitter, T* Lop, T* UHB, const int* prev_info, int* info, int Bt,      \
-                                               int N, int n, int m, int kernel_kind, void* stream) {                         \
-        if (Bt <= 0) return BCBF_OK;                                                                                         \
-        if (!X || !UH || !Bm || !ell || !s2 || !UHB || !prev_info || prev_info == info) return BCBF_EINVAL;                  \
-        if (kernel_kind < 0 || kernel_kind >= bcbf::BCBF_KINDS) return BCBF_EINVAL;                                          \
-        bcbf::g_refit_only_bad = prev_info;                                                                                  \
-        const int rc = kernel_kind == 0 ? bcbf_refit_mfma_##SUF(X, UH, Bm, ell, s2, jitter, nullptr, Lop, UHB, nullptr, info, \
-                                                                Bt, N, n, m, stream)                                         \
-                     : kernel_kind == 1 ? bcbf_refit_matern52_##SUF(X, UH, Bm, ell, s2, jitter, Lop, UHB, nullptr, info, Bt,  \
-                                                                    N, n, m, stream)                                         \
-                                        : bcbf_refit_rbfm52_##SUF(X, UH, Bm, ell, s2, jitter, Lop, UHB, nullptr, info, Bt, N, \
-                                                                  n, m, stream);                                             \
-        bcbf::g_refit_only_bad = nullptr;                                                                                    \
-        return rc;                                                                                                           \
-    }
-BCBF_REFIT_RETRY_KIND(f32, float)
-BCBF_REFIT_RETRY_KIND(f64, double)
-#undef BCBF_REFIT_RETRY_KIND
-namespace bcbf {
-int launch_refit_team32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                        const float* jitter, const float* Kdense, float* Lop, float* UHB, float* Ldense, int* info, int Bt, int N,
-                        int Np, int n, int C, int nw, hipStream_t st) {
-    return launch_refit_team<float>(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, nw, st);
-}
-
-// Called by bcbf_refit_mfma_f64 / _f32 for batches.
+// One wave per instance.  plan.waves_per_simd: the register allocation the kernel is compiled for (fp32 only; fp64:
+// BCBF_RW64_OCC); plan.super_panels: the 64-column super-panel instantiation (a build with BCBF_RW32_SUPER / BCBF_RW64_SUPER
+// off never runs it).
 template <typename T>
-static int launch_refit_wave(const T* X, const T* UH, const T* Bm, const T* ell, const T* s2, const T* jitter,
-                             const T* Kdense, T* Lop, T* UHB, T* Ldense, int* info, int Bt, int N, int Np, int n, int C,
-                             hipStream_t st) {
-    const dim3 grid((Bt + RW_WPB - 1) / RW_WPB), block(64 * RW_WPB);
-    int dev_ = 0, cus = 256;
-    (void)hipGetDevice(&dev_);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_);
-    bool two = sizeof(T) == 4 && Bt >= 8 * cus && Np < 1024;   // more than one instance per SIMD (N >= 1024: one wave with all 512
-                                                               // registers is faster even then, 4096 x 1024: 20.7 against 21.6 ms)
-    if (const char* e = getenv("BCBF_RW32_OCC")) two = e[0] == '2';      // (development: force the allocation)
+int launch_refit_wave(const RefitArgs<T>& a, const RefitPlan& plan) {
+    const dim3 grid((a.Bt + RW_WPB - 1) / RW_WPB), block(64 * RW_WPB);
 #define BCBF_RW_LAUNCH(OCC_, ...)                                                                                         \
     do {                                                                                                                  \
-        if (Kdense)                                                                                                       \
-            hipLaunchKernelGGL((refit_wave_kernel<T, true, OCC_>), grid, block, 0, st, nullptr, nullptr, nullptr, nullptr,  \
-                               nullptr, nullptr, Kdense, Lop, nullptr, Ldense, info, Bt, N, Np, 0, 0, g_refit_only_bad);                    \
+        if (a.Kdense)                                                                                                     \
+            hipLaunchKernelGGL((refit_wave_kernel<T, true, OCC_>), grid, block, 0, a.stream, nullptr, nullptr, nullptr, nullptr,  \
+                               nullptr, nullptr, a.Kdense, a.Lop, nullptr, a.Ldense, a.info, a.Bt, a.N, a.Np, 0, 0, a.only_bad);   \
         else                                                                                                              \
-            hipLaunchKernelGGL((refit_wave_kernel<T, false, OCC_, ##__VA_ARGS__>), grid, block, 0, st, X, UH, Bm, ell, s2, jitter,        \
-                               nullptr, Lop, UHB, Ldense, info, Bt, N, Np, n, C, g_refit_only_bad);                                         \
+            hipLaunchKernelGGL((refit_wave_kernel<T, false, OCC_, ##__VA_ARGS__>), grid, block, 0, a.stream, a.X, a.UH, a.Bm, a.ell, a.s2, \
+                               a.jitter, nullptr, a.Lop, a.UHB, a.Ldense, a.info, a.Bt, a.N, a.Np, a.n, a.C, a.only_bad);           \
     } while (0)
     if constexpr (sizeof(T) == 4) {
-        // super-panels from N = 512 on (BCBF_RW32_SUPER; never for a given dense K_b or a dense output: those are the
-        // few-system paths)
-        bool sup = BCBF_RW32_SUPER && BCBF_RW32_PAIRS && Np >= 512 && !Kdense && !Ldense;
-        if (const char* e = getenv("BCBF_RW32_SUPER_FORCE")) sup = e[0] == '1' && !Kdense;      // (development)
+        const bool sup = BCBF_RW32_SUPER && BCBF_RW32_PAIRS && plan.super_panels && !a.Kdense, two = plan.waves_per_simd == 2;
         if (sup) { if (two) BCBF_RW_LAUNCH(2, true); else BCBF_RW_LAUNCH(1, true); }
         else { if (two) BCBF_RW_LAUNCH(2); else BCBF_RW_LAUNCH(1); }
     } else {
-        // fp64: from N = 1024 (1024 x 1024 14.5 -> 12.7 ms; at N = 512 the four fp64 tiles -- 128 accumulator registers -- cost
-        // more than the halved panel reads save: 4096 x 512 7.35 -> 9.1 ms)
-        bool sup = BCBF_RW64_SUPER && Np >= 1024 && !Kdense && !Ldense;
-        if (const char* e = getenv("BCBF_RW64_SUPER_FORCE")) sup = e[0] == '1' && !Kdense;      // (development)
+        const bool sup = BCBF_RW64_SUPER && plan.super_panels && !a.Kdense;
         if (sup) BCBF_RW_LAUNCH(BCBF_RW64_OCC, true); else BCBF_RW_LAUNCH(BCBF_RW64_OCC);
     }
 #undef BCBF_RW_LAUNCH
     return 0;
 }
-int launch_refit_wave64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
-                        const double* jitter, const double* Kdense, double* Lop, double* UHB, double* Ldense, int* info,
-                        int Bt, int N, int Np, int n, int C, hipStream_t st) {
-    return launch_refit_wave<double>(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, st);
-}
-int launch_refit_wave32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
-                        const float* jitter, const float* Kdense, float* Lop, float* UHB, float* Ldense, int* info,
-                        int Bt, int N, int Np, int n, int C, hipStream_t st) {
-    return launch_refit_wave<float>(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ldense, info, Bt, N, Np, n, C, st);
-}
+template int launch_refit_wave<float>(const RefitArgs<float>&, const RefitPlan&);
+template int launch_refit_wave<double>(const RefitArgs<double>&, const RefitPlan&);
 
 }  // namespace bcbf

@@ -104,10 +104,25 @@ def _kern(base, kernel):
     return base + _KSUF[kernel]
 
 
-def refit(X, UH, Bm, ell, s2, jitter=None, want_dense=False, out=None, kernel="rbf"):
+# Launch forms of the refit (bcbf.h: BCBF_FORM_*).  form=None is AUTO -- the library's measured choice; the others are for parity
+# tests and measurements.  REFIT_WAVE takes one REFIT_SUPER_* and one REFIT_OCC* value or-ed in (64-column super-panels on / off,
+# register allocation for 1 / 2 waves per SIMD).
+REFIT_AUTO, REFIT_WORKGROUP, REFIT_WAVE, REFIT_PAIR, REFIT_TEAM4, REFIT_TEAM8 = range(6)
+REFIT_SUPER_ON, REFIT_SUPER_OFF, REFIT_OCC1, REFIT_OCC2 = 0x10, 0x20, 0x40, 0x80
+
+
+def _refit_form(X, UH, Bm, ell, s2, jitter, Kdense, Lop, UHB, Ld, prev_info, info, Bt, N, n, m, kernel, form, like):
+    """bcbf_refit_form: the one entry behind refit, refit_retry and potrf."""
+    _kern("", kernel)
+    check(getattr(lib, "bcbf_refit_form" + _suf(like))(_p(X), _p(UH), _p(Bm), _p(ell), _p(s2), _p(jitter), _p(Kdense), _p(Lop), _p(UHB),
+                                                       _p(Ld), _p(prev_info), _p(info), Bt, N, n, m, DATA_KERNELS.index(kernel),
+                                                       REFIT_AUTO if form is None else int(form), _stream(like)), "bcbf_refit_form")
+
+
+def refit(X, UH, Bm, ell, s2, jitter=None, want_dense=False, out=None, kernel="rbf", form=None):
     """Fused K_b build + Cholesky + packing.  Returns (Lop[Bt,E], UHB[Bt,N,C], info[Bt], Ldense|None).
     out = (Lop, UHB, info): write into the caller's buffers (a closed loop that has bound their addresses).
-    kernel="matern52": the opt-in Matern-5/2 data kernel (bcbf_refit_matern52)."""
+    kernel="matern52": the opt-in Matern-5/2 data kernel.  form: a REFIT_* launch form (None: the library chooses)."""
     _chk(X, UH, Bm, ell, s2, jitter)
     Bt, N, n = X.shape
     C = UH.shape[2]
@@ -120,24 +135,20 @@ def refit(X, UH, Bm, ell, s2, jitter=None, want_dense=False, out=None, kernel="r
         UHB = torch.empty(Bt, N, C, dtype=X.dtype, device=X.device)
         info = torch.empty(Bt, dtype=torch.int32, device=X.device)
     Ld = torch.empty(Bt, N, N, dtype=X.dtype, device=X.device) if want_dense else None
-    check(getattr(lib, _kern("bcbf_refit", kernel) + _suf(X))(_p(X), _p(UH), _p(Bm), _p(ell), _p(s2), _p(jitter), _p(Lop), _p(UHB),
-                                                              _p(Ld), _p(info), Bt, N, n, C - 1, _stream(X)), "bcbf_refit")
+    if Bt > 0:
+        _refit_form(X, UH, Bm, ell, s2, jitter, None, Lop, UHB, Ld, None, info, Bt, N, n, C - 1, kernel, form, X)
     return Lop, UHB, info, Ld
 
 
-def refit_retry(X, UH, Bm, ell, s2, jitter, Lop, UHB, prev_info, info, kernel="rbf"):
-    """Factor again ONLY the instances with prev_info[b] != 0 (bcbf_refit_retry; no host round trip), with the jitter the
-    caller has raised for them; writes `info` (a different buffer than prev_info)."""
+def refit_retry(X, UH, Bm, ell, s2, jitter, Lop, UHB, prev_info, info, kernel="rbf", form=None):
+    """Factor again ONLY the instances with prev_info[b] != 0 (no host round trip), with the jitter the caller has raised
+    for them; writes `info` (a different buffer than prev_info)."""
     _chk(X, UH, Bm, ell, s2, jitter, Lop, UHB, prev_info, info)
     Bt, N, n = X.shape
-    if kernel != "rbf":
-        _kern("", kernel)
-        check(getattr(lib, "bcbf_refit_retry_kind" + _suf(X))(_p(X), _p(UH), _p(Bm), _p(ell), _p(s2), _p(jitter), _p(Lop), _p(UHB),
-                                                              _p(prev_info), _p(info), Bt, N, n, UH.shape[2] - 1,
-                                                              DATA_KERNELS.index(kernel), _stream(X)), "bcbf_refit_retry_kind")
-        return info
-    check(getattr(lib, "bcbf_refit_retry" + _suf(X))(_p(X), _p(UH), _p(Bm), _p(ell), _p(s2), _p(jitter), _p(Lop), _p(UHB),
-                                                     _p(prev_info), _p(info), Bt, N, n, UH.shape[2] - 1, _stream(X)), "bcbf_refit_retry")
+    if prev_info is None:
+        raise ValueError("refit_retry: prev_info is required")
+    if Bt > 0:
+        _refit_form(X, UH, Bm, ell, s2, jitter, None, Lop, UHB, None, prev_info, info, Bt, N, n, UH.shape[2] - 1, kernel, form, X)
     return info
 
 
@@ -199,14 +210,15 @@ def predict_fullmat(Lop, Vw, X, UHB, ell, s2, Bm, M0, A, Xq, jitter=None, want_B
     return Mk, BkXX, Kron
 
 
-def potrf(Kb, want_dense=False):
+def potrf(Kb, want_dense=False, form=None):
     """Cholesky of caller-supplied SPD matrices (torch.linalg.cholesky, control_affine_model.py:911)."""
     _chk(Kb)
     Bt, N, _ = Kb.shape
     Lop = torch.empty(Bt, lop_elems(N, Kb.dtype), dtype=Kb.dtype, device=Kb.device)
     info = torch.empty(Bt, dtype=torch.int32, device=Kb.device)
     Ld = torch.empty(Bt, N, N, dtype=Kb.dtype, device=Kb.device) if want_dense else None
-    check(getattr(lib, "bcbf_potrf" + _suf(Kb))(_p(Kb), _p(Lop), _p(Ld), _p(info), Bt, N, _stream(Kb)), "bcbf_potrf")
+    if Bt > 0:
+        _refit_form(None, None, None, None, None, None, Kb, Lop, None, Ld, None, info, Bt, N, 0, 0, "rbf", form, Kb)
     return Lop, info, Ld
 
 

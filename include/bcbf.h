@@ -129,6 +129,46 @@ int bcbf_refit_retry_kind_f64(const double* X, const double* UH, const double* B
                               const double* jitter, double* Lop, double* UHB, const int* prev_info, int* info,
                               int Bt, int N, int n, int m, int kernel_kind, void* stream);
 
+/* The general refit entry: bcbf_refit, bcbf_refit_retry[_kind], bcbf_refit_matern52 / _rbfm52 and bcbf_potrf are this call with
+ * form = BCBF_FORM_AUTO.  Kdense != NULL: factor the caller's K_b[Bt,N,N] (bcbf_potrf: X .. jitter, UHB, n, m unused);
+ * prev_info != NULL: the retry (factor only the instances with prev_info[b] != 0; prev_info == info is refused);
+ * kernel_kind: 0 RBF, 1 Matern-5/2, 2 RBF x Matern-5/2.  BCBF_EINVAL before any launch for a null required pointer, N < 1,
+ * n or m out of range (without Kdense), a kernel_kind or form that does not exist, or a form refused below -- these checks
+ * run before the Bt <= 0 early return (the older entries return BCBF_OK for Bt <= 0 before they look at anything else).
+ *
+ * `form` = one of the launch forms below, optionally or-ed with one BCBF_FORM_SUPER_* and one BCBF_FORM_OCC* value.  The
+ * library measures and chooses (AUTO); the others exist for parity tests and measurements, and every form computes the same
+ * factor (to rounding: the forms accumulate in different orders).  The choice depends on the arguments and the device's
+ * compute-unit count only -- never on the process environment.
+ *   WORKGROUP  one workgroup of 4 or 8 waves per instance; always honoured.
+ *   WAVE       one wave per instance; always honoured.
+ *   PAIR       two waves per instance; runs WAVE with a dense input or output (Kdense / Ldense) or N > 512.
+ *   TEAM4/8    a chain wave + three / seven bulk waves per instance; TEAM4 from Kdense runs TEAM8; N > 8192: BCBF_EINVAL.
+ *   kernel_kind != 0 has one form, TEAM8 (no Kdense, N <= 8192): any form but AUTO / TEAM8 is BCBF_EINVAL.
+ * Sub-forms of WAVE (ignored by the other forms): 64-column super-panels on / off (on is honoured unless Kdense), and the
+ * register allocation for 1 / 2 waves per SIMD (fp32 only; fp64 always runs 1). */
+#define BCBF_FORM_AUTO 0
+#define BCBF_FORM_WORKGROUP 1
+#define BCBF_FORM_WAVE 2
+#define BCBF_FORM_PAIR 3
+#define BCBF_FORM_TEAM4 4
+#define BCBF_FORM_TEAM8 5
+#define BCBF_FORM_SUPER_ON 0x10
+#define BCBF_FORM_SUPER_OFF 0x20
+#define BCBF_FORM_OCC1 0x40
+#define BCBF_FORM_OCC2 0x80
+int bcbf_refit_form_f32(const float* X, const float* UH, const float* Bm, const float* ell, const float* s2,
+                        const float* jitter, const float* Kdense, float* Lop, float* UHB, float* Ldense,
+                        const int* prev_info, int* info, int Bt, int N, int n, int m, int kernel_kind, int form, void* stream);
+int bcbf_refit_form_f64(const double* X, const double* UH, const double* Bm, const double* ell, const double* s2,
+                        const double* jitter, const double* Kdense, double* Lop, double* UHB, double* Ldense,
+                        const int* prev_info, int* info, int Bt, int N, int n, int m, int kernel_kind, int form, void* stream);
+/* What bcbf_refit_form would launch on a device of `cus` compute units: out_plan[4] (host) = { form (never AUTO), waves per
+ * instance, waves per SIMD (WAVE only, else 0), super-panels 0 / 1 }.  A host function: no device call.  BCBF_EINVAL (reason
+ * in bcbf_last_error) where bcbf_refit_form refuses the form. */
+int bcbf_refit_plan(int is_f64, int Bt, int N, int cus, int has_Kdense, int has_Ldense, int kernel_kind, int form,
+                    int* out_plan);
+
 /* Random max_train subset of a learning loop's observation pool, selected and gathered in one launch: the reference's
  * `np.random.shuffle(indices)` + `shuffled_indices[:max_train]` (LearnedShiftInvariantDynamics.fit,
  * unicycle_move_to_pose.py:377-384) with the randomness supplied by the caller.  keys[B, ldk]: one draw per pool row (uniform

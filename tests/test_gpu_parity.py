@@ -1047,11 +1047,11 @@ def test_fp64_shared_queries_two_per_workgroup(ops, m):
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("N,n,m", [(1, 2, 1), (31, 3, 2), (33, 3, 2), (100, 2, 1), (256, 2, 1), (512, 3, 2), (700, 3, 3)])
-def test_refit_one_wave_per_instance_vs_oracle_and_workgroup_form(ops, N, n, m, dtype, monkeypatch):
+def test_refit_one_wave_per_instance_vs_oracle_and_workgroup_form(ops, N, n, m, dtype):
     """The batch form of the refit (refit_wave64.hip: one wave per instance, 4-column-blocked diagonal tiles; fp64 and fp32;
     a batch of 70 runs one wave per SIMD, the two-waves-per-SIMD fp32 allocation is covered by the C3 test) against
     the oracle's factor and against the workgroup-per-instance form (refit_mfma64.hip / refit_mfma.hip) on the same inputs: dense L,
-    packed operator (incl. the inverted diagonal blocks), UH*B, per-instance failure index.  BCBF_REFIT_WAVE forces the
+    packed operator (incl. the inverted diagonal blocks), UH*B, per-instance failure index.  `form=` forces the
     form (the library picks by batch size)."""
     from bayesian_cbf_amd.synthetic import make_instances
     Bt = 70                                    # odd number of workgroups' worth of waves + a ragged tail
@@ -1068,12 +1068,10 @@ def test_refit_one_wave_per_instance_vs_oracle_and_workgroup_form(ops, N, n, m, 
         jit[5] = 0.0
         jit[5, 20] = -1e-3 if f64 else -1e-2
     args = (X, UH, p["Bm"], p["ell"], p["s2"], jit)
-    monkeypatch.setenv("BCBF_REFIT_WAVE", "1")
-    Lop_w, UHB_w, info_w, Ld_w = ops.refit(*args, want_dense=True)
+    Lop_w, UHB_w, info_w, Ld_w = ops.refit(*args, want_dense=True, form=ops.REFIT_WAVE)
     Kb = ops.kb_build(*args)
-    Lop_p, info_p, Ld_p = ops.potrf(Kb, want_dense=True)            # the from-dense instantiation of the same kernel
-    monkeypatch.setenv("BCBF_REFIT_WAVE", "0")
-    Lop_g, UHB_g, info_g, Ld_g = ops.refit(*args, want_dense=True)
+    Lop_p, info_p, Ld_p = ops.potrf(Kb, want_dense=True, form=ops.REFIT_WAVE)   # the from-dense instantiation of the same kernel
+    Lop_g, UHB_g, info_g, Ld_g = ops.refit(*args, want_dense=True, form=ops.REFIT_WORKGROUP)
     torch.cuda.synchronize()
     iw = info_w.cpu().numpy()
     assert np.array_equal(iw, info_g.cpu().numpy()) and np.array_equal(iw, info_p.cpu().numpy())
@@ -1111,10 +1109,10 @@ def test_refit_one_wave_per_instance_vs_oracle_and_workgroup_form(ops, N, n, m, 
                                           ("team", 1, 1, 2, 1), ("team", 7, 33, 3, 2), ("team", 3, 100, 6, 3), ("team", 9, 500, 3, 2),
                                           ("team", 2, 1000, 3, 3), ("team", 1, 2048, 3, 2),
                                           ("team4", 7, 33, 3, 2), ("team4", 5, 300, 6, 3), ("team4", 2, 500, 3, 2)])
-def test_refit_two_waves_per_instance_vs_one_wave_form_and_oracle(ops, form, Bt, N, n, m, dtype, monkeypatch):
+def test_refit_two_waves_per_instance_vs_one_wave_form_and_oracle(ops, form, Bt, N, n, m, dtype):
     """The chain + bulk forms of the refit (refit_wave64.hip: a chain wave that factors and inverts the diagonal tiles on the
     matrix cores; `pair`: one bulk wave a block column behind, N <= 512; `team` / `team4`: seven / three bulk waves sharing a
-    column's tiles, hand-offs per block row, N <= 2048) forced by BCBF_REFIT_PAIR=1 / BCBF_REFIT_TEAM=1 against the
+    column's tiles, hand-offs per block row, N <= 2048) forced by `form=` against the
     one-wave form on the same inputs -- packed operator incl. both copies of the inverted diagonal blocks, UH*B,
     per-instance failure index (a failed pivot in one instance) -- and, through potrs + the posterior kernel, against the
     oracle.  Shapes: one row, a ragged last block, a state wider than the registers hold (n = 6), the largest systems of
@@ -1131,16 +1129,9 @@ def test_refit_two_waves_per_instance_vs_one_wave_form_and_oracle(ops, form, Bt,
         jit[5] = 0.0
         jit[5, 20] = -1e-3 if f64 else -1e-2
     args = (X, UH, p["Bm"], p["ell"], p["s2"], jit)
-    if form == "pair":
-        monkeypatch.setenv("BCBF_REFIT_WAVE", "1")
-        monkeypatch.setenv("BCBF_REFIT_PAIR", "1")
-    else:
-        monkeypatch.setenv("BCBF_REFIT_TEAM", "14" if form == "team4" else "18")   # (four / eight waves per instance)
-    Lop_p, UHB_p, info_p, _ = ops.refit(*args)
-    monkeypatch.setenv("BCBF_REFIT_TEAM", "0")
-    monkeypatch.setenv("BCBF_REFIT_WAVE", "1")
-    monkeypatch.setenv("BCBF_REFIT_PAIR", "0")
-    Lop_w, UHB_w, info_w, _ = ops.refit(*args)
+    forced = {"pair": ops.REFIT_PAIR, "team4": ops.REFIT_TEAM4, "team": ops.REFIT_TEAM8}[form]   # (two / four / eight waves per instance)
+    Lop_p, UHB_p, info_p, _ = ops.refit(*args, form=forced)
+    Lop_w, UHB_w, info_w, _ = ops.refit(*args, form=ops.REFIT_WAVE)
     torch.cuda.synchronize()
     ip = info_p.cpu().numpy()
     assert np.array_equal(ip, info_w.cpu().numpy())
@@ -1165,7 +1156,7 @@ def test_refit_two_waves_per_instance_vs_one_wave_form_and_oracle(ops, form, Bt,
 
 @pytest.mark.parametrize("dtype,N,n,m", [(torch.float64, 1024, 3, 2), (torch.float64, 1100, 2, 1), (torch.float32, 512, 3, 2),
                                          (torch.float32, 1000, 4, 3), (torch.float32, 576, 3, 1)], ids=["f64-1024", "f64-1100", "f32-512", "f32-1000", "f32-576"])
-def test_refit_super_panel_form_equals_plain_form(ops, dtype, N, n, m, monkeypatch):
+def test_refit_super_panel_form_equals_plain_form(ops, dtype, N, n, m):
     """One-wave refit: the 64-column super-panel instantiation (2 x 2 tiles per stream pass, lean value pass, in-register second
     update) against the plain instantiation of the same kernel on the same inputs, entry by entry -- incl. a ragged last block
     and an odd number of block columns -- and per-instance failure index.  (The super-panel fp64 instantiation sits at 256 + 256
@@ -1174,12 +1165,9 @@ def test_refit_super_panel_form_equals_plain_form(ops, dtype, N, n, m, monkeypat
     f64 = dtype == torch.float64
     p = make_instances(6, N, n, m, dtype=dtype, device=DEV, seed=900 + N)
     args = (p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])
-    monkeypatch.setenv("BCBF_REFIT_WAVE", "1")
-    key = "BCBF_RW64_SUPER_FORCE" if f64 else "BCBF_RW32_SUPER_FORCE"
-    monkeypatch.setenv(key, "1")
-    Lop_s, UHB_s, info_s, _ = ops.refit(*args)
-    monkeypatch.setenv(key, "0")
-    Lop_p, UHB_p, info_p, _ = ops.refit(*args)
+    sup, plain = ops.REFIT_WAVE | ops.REFIT_SUPER_ON, ops.REFIT_WAVE | ops.REFIT_SUPER_OFF
+    Lop_s, UHB_s, info_s, _ = ops.refit(*args, form=sup)
+    Lop_p, UHB_p, info_p, _ = ops.refit(*args, form=plain)
     torch.cuda.synchronize()
     assert torch.equal(info_s, info_p) and int((info_s == 0).sum()) >= 4     # (a system that fp32 cannot factor fails in both forms alike)
     assert torch.equal(UHB_s, UHB_p)
@@ -1192,64 +1180,62 @@ def test_refit_super_panel_form_equals_plain_form(ops, dtype, N, n, m, monkeypat
         # fp32 again with a jitter of order 1 on the diagonal: K_b is then well conditioned, the two forms agree to rounding, and
         # a jitter entry that went missing or to the wrong row would stand out
         big = (p["jitter"] * 5e4).contiguous()
-        monkeypatch.setenv(key, "1")
-        Lb_s, _, ib_s, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], big)
-        monkeypatch.setenv(key, "0")
-        Lb_p, _, ib_p, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], big)
+        Lb_s, _, ib_s, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], big, form=sup)
+        Lb_p, _, ib_p, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], big, form=plain)
         torch.cuda.synchronize()
         assert int((ib_s != 0).sum()) == 0 and int((ib_p != 0).sum()) == 0
         for i in range(6):
             rel_close(host(Lb_s[i]), host(Lb_p[i]), 2e-5, what="super-panel vs plain form, large jitter [%d]" % i)
 
 
-@pytest.mark.parametrize("Bt,N,n,m", [(9, 512, 3, 2), (5, 500, 3, 2), (6, 448, 4, 2), (4, 130, 2, 1), (3, 490, 3, 3)])
-def test_refit_slab_form_vs_one_wave_form_and_oracle(ops, Bt, N, n, m, monkeypatch):
-    """The four-waves-per-instance form of the fp32 refit whose update operands are staged through LDS by `buffer_load ... lds`
-    (refit_slab.hip; experimental, BCBF_REFIT_SLAB=1 -- DESIGN_NOTES round 6: correct, slower than the one-wave form) against the
-    one-wave form on the same inputs: failure index (a failed pivot in one instance), UH*B, the packed operator to cond x eps, and
-    through potrs + the posterior kernel against the oracle.  Shapes: full super-panels, a ragged last block, n = 4, an odd count
-    of 32-row blocks padded to an even one, C = 4."""
+_RETRY_FORMS = [("workgroup", "rbf"), ("wave", "rbf"), ("pair", "rbf"), ("team4", "rbf"), ("team8", "rbf"),
+                ("team8", "matern52"), ("team8", "rbf_matern52")]
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("Bt,N,n,m", [(7, 33, 3, 2), (7, 100, 2, 1)])
+@pytest.mark.parametrize("form,kernel", _RETRY_FORMS, ids=["%s-%s" % fk for fk in _RETRY_FORMS])
+def test_refit_retry_factors_only_failed_instances_in_every_form(ops, form, kernel, Bt, N, n, m, dtype):
+    """The retry's prev_info reaches the kernel of EVERY launch form (an explicit launcher argument): after a launch in which
+    instance 5 fails at pivot 21, the operators of the six good instances are overwritten with a sentinel, instance 5's
+    jitter is repaired and the retry runs under the same form -- info all zero, the sentinel rows bit for bit untouched (a
+    launcher that lost prev_info would factor the whole batch again), row 5 equal to a fresh full refit with the repaired
+    jitter.  Shapes: the smallest with a ragged second block, and with more than one block row."""
     from bayesian_cbf_amd.synthetic import make_instances
-    p = make_instances(Bt, N, n, m, dtype=torch.float32, device=DEV, seed=700 + N)
-    jit = p["jitter"].clone()
-    X, UH = p["X"].clone(), p["UH"].clone()
-    X[2, 70], UH[2, 70] = X[2, 3], UH[2, 3]          # instance 2: a duplicated point with a negative shift -> pivot 71 fails
-    jit[2] = 0.0
-    jit[2, 70] = -1e-2
-    args = (X, UH, p["Bm"], p["ell"], p["s2"], jit)
-    monkeypatch.setenv("BCBF_REFIT_SLAB", "1")
-    Lop_s, UHB_s, info_s, _ = ops.refit(*args)
-    monkeypatch.delenv("BCBF_REFIT_SLAB")
-    monkeypatch.setenv("BCBF_REFIT_WAVE", "1")
-    Lop_w, UHB_w, info_w, _ = ops.refit(*args)
+    f64 = dtype == torch.float64
+    forced = {"workgroup": ops.REFIT_WORKGROUP, "wave": ops.REFIT_WAVE, "pair": ops.REFIT_PAIR, "team4": ops.REFIT_TEAM4,
+              "team8": ops.REFIT_TEAM8}[form]
+    p = make_instances(Bt, N, n, m, dtype=dtype, device=DEV, seed=100 + N)
+    X, UH, jit = (p["X"] * 2.0).contiguous(), p["UH"].clone(), p["jitter"].clone()
+    X[5, 20], UH[5, 20] = X[5, 3], UH[5, 3]    # instance 5: a duplicated point with a negative shift -> pivot 21 fails
+    jit[5] = 0.0
+    jit[5, 20] = -1e-3 if f64 else -1e-2
+    Lop, UHB, info, _ = ops.refit(X, UH, p["Bm"], p["ell"], p["s2"], jit, kernel=kernel, form=forced)
+    want = [0] * Bt
+    want[5] = 21
+    assert info.tolist() == want
+    good = torch.arange(Bt, device=DEV) != 5
+    Lop[good] = 7.25                            # the sentinel
+    jit[5] = p["jitter"][5]
+    jit[5, 20] = 1e-3 if f64 else 1e-2          # repaired: the shift with its sign turned
+    info2 = torch.full_like(info, 77)
+    ops.refit_retry(X, UH, p["Bm"], p["ell"], p["s2"], jit, Lop, UHB, info, info2, kernel=kernel, form=forced)
+    Lref, _, iref, _ = ops.refit(X, UH, p["Bm"], p["ell"], p["s2"], jit, kernel=kernel, form=forced)
     torch.cuda.synchronize()
-    is_ = info_s.cpu().numpy()
-    assert np.array_equal(is_, info_w.cpu().numpy()) and is_[2] == 71 and (is_ == 0).sum() == Bt - 1
-    assert torch.equal(UHB_s, UHB_w)
-    for i in np.nonzero(is_ == 0)[0]:
-        rel_close(host(Lop_s[i]), host(Lop_w[i]), 2e-3, what="Lop vs one-wave form [%d]" % i)
-    Vw, _ = ops.potrs(Lop_s, p["Xdot"], UH, p["M0"], want_alpha=False)
-    Mk, Bk = ops.posterior_step(Lop_s, Vw, X, UHB_s, p["ell"], p["s2"], p["Bm"], p["M0"], p["xq"])
-    h = {k: host(v) for k, v in dict(X=X, U=p["U"], Xdot=p["Xdot"], Bm=p["Bm"], ell=p["ell"], s2=p["s2"], M0=p["M0"], jit=jit).items()}
-    for i in (0, 1):                                   # (instance 2 is the failed one)
-        st = ogp.refit_state(h["X"][i], h["U"][i], h["Xdot"][i], h["Bm"][i], h["ell"][i], h["s2"][i], h["M0"][i],
-                             h["jit"][i][None] / 1e-5)
-        Mk_o, Bk_o = ogp.posterior_step(st["L"][None], st["alpha"][None], h["X"][i][None], st["UHB"][None], h["ell"][i][None],
-                                        h["s2"][i][None], h["Bm"][i][None], h["M0"][i][None], host(p["xq"])[i][None])
-        rel_close(host(Mk)[i], Mk_o[0], 1e-3, scale=max(1.0, np.abs(Mk_o).max()), what="Mk")
-        rel_close(host(Bk)[i], Bk_o[0], 1e-3, scale=float(h["s2"][i] * np.abs(h["Bm"][i]).max()), what="Bk")
+    assert info2.tolist() == [0] * Bt and iref.tolist() == [0] * Bt
+    assert torch.equal(Lop[good], torch.full_like(Lop[good], 7.25))
+    rel_close(host(Lop[5]), host(Lref[5]), 1e-8 if f64 else 1e-3, what="retried operator vs fresh refit")
 
 
 @pytest.mark.timeout(180)
-def test_refit_handoff_protocols_soak(ops, monkeypatch):
+def test_refit_handoff_protocols_soak(ops):
     """The chain / bulk refit kernels hand work over through spin waits on LDS counters; a lost wake-up would be a hang.
     A few hundred synchronised launches over random shapes, precisions, forms (library's choice, two waves, team of eight /
     four, one wave), dense outputs and failed pivots in random places (the long version: tools/stress_refit.py); every
     launch must come back, and the failure index must not depend on the form."""
     from bayesian_cbf_amd.synthetic import make_instances
     rng = np.random.default_rng(7)
-    forms = {"default": {}, "pair": {"BCBF_REFIT_WAVE": "1", "BCBF_REFIT_PAIR": "1"}, "team8": {"BCBF_REFIT_TEAM": "18"},
-             "team4": {"BCBF_REFIT_TEAM": "14"}, "wave": {"BCBF_REFIT_WAVE": "1", "BCBF_REFIT_PAIR": "0"}}
+    forms = {"default": None, "pair": ops.REFIT_PAIR, "team8": ops.REFIT_TEAM8, "team4": ops.REFIT_TEAM4, "wave": ops.REFIT_WAVE}
     launches = 0
     for _ in range(40):
         dtype = torch.float64 if rng.random() < 0.5 else torch.float32
@@ -1261,13 +1247,10 @@ def test_refit_handoff_protocols_soak(ops, monkeypatch):
         for _k in range(int(rng.integers(0, 3))):
             jit[int(rng.integers(Bt)), int(rng.integers(N))] = -10.0
         infos = {}
-        for name, env in forms.items():
-            for k in ("BCBF_REFIT_TEAM", "BCBF_REFIT_WAVE", "BCBF_REFIT_PAIR"):
-                monkeypatch.delenv(k, raising=False)
-            for k, v in env.items():
-                monkeypatch.setenv(k, v)
+        for name, form in forms.items():
             for _rep in range(2):
-                _, _, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], jit, want_dense=bool(rng.random() < 0.2 and N <= 300))
+                _, _, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], jit, want_dense=bool(rng.random() < 0.2 and N <= 300),
+                                          form=form)
                 torch.cuda.synchronize()
                 launches += 1
             infos[name] = info.cpu().numpy()

@@ -139,7 +139,9 @@ LQR_OK = [dict(), dict(u0=None), dict(n=4, m=3), dict(n=1, m=1), dict(t=25), dic
 LQR_BAD = [dict(n=0), dict(n=5), dict(m=0), dict(m=4), dict(Mk=None), dict(Mj=None), dict(x=None), dict(x_goal=None),
            dict(Q=None), dict(R=None), dict(u=None), dict(status=None), dict(dt=0.0), dict(dt=-0.01), dict(dt=float("nan")),
            dict(numSteps=0), dict(t=-1), dict(Bt=-1)]
-_ids = lambda d: ",".join("%s=%s" % (k, "ptr" if isinstance(v, ctypes.c_void_p) else v) for k, v in d.items()) or "default"  # noqa: E731
+# (a ctypes array prints with its address, which would give the case a different id in every process)
+_ids = lambda d: ",".join("%s=%s" % (k, "ptr" if isinstance(v, ctypes.c_void_p) else "array" if isinstance(v, ctypes.Array) else v)  # noqa: E731
+                          for k, v in d.items()) or "default"
 
 
 @pytest.mark.parametrize("suf, ct", [("_f32", ctypes.c_float), ("_f64", ctypes.c_double)], ids=["f32", "f64"])

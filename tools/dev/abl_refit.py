@@ -13,7 +13,7 @@ def build():
     ps = []
     for name, fl in VARIANTS.items():
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-               "-I" + CSRC] + fl + [os.path.join(CSRC, "refit_mfma.hip"), os.path.join(CSRC, "common.hip"), "-o", os.path.join(VDIR, "rm_" + name + ".so")]
+               "-I" + CSRC] + fl + [os.path.join(CSRC, f) for f in ("refit.hip", "refit_mfma.hip", "refit_mfma64.hip", "refit_wave64.hip", "common.hip")] + ["-o", os.path.join(VDIR, "rm_" + name + ".so")]
         ps.append(subprocess.Popen(cmd))
     assert all(p.wait() == 0 for p in ps)
 def run():
@@ -30,8 +30,8 @@ def run():
     for name in VARIANTS:
         lib = ctypes.CDLL(os.path.join(VDIR, "rm_" + name + ".so"))
         def call():
-            rc = lib.bcbf_refit_mfma_f32(q(p["X"]), q(p["UH"]), q(p["Bm"]), q(p["ell"]), q(p["s2"]), q(p["jitter"]), None, q(Lop), q(UHB), None, q(info),
-                                         Bt, N, n, C - 1, P(torch.cuda.current_stream().cuda_stream)); assert rc == 0
+            rc = lib.bcbf_refit_form_f32(q(p["X"]), q(p["UH"]), q(p["Bm"]), q(p["ell"]), q(p["s2"]), q(p["jitter"]), None, q(Lop), q(UHB), None, None, q(info),
+                                         Bt, N, n, C - 1, 0, ops.REFIT_WORKGROUP, P(torch.cuda.current_stream().cuda_stream)); assert rc == 0
         call(); torch.cuda.synchronize(); t0 = time.perf_counter()
         for _ in range(3): call()
         torch.cuda.synchronize()

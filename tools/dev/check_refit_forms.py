@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The two-waves-per-instance form of the refit (BCBF_REFIT_PAIR=1) against the one-wave form, element by element (development):
+"""The two-waves-per-instance form of the refit (form=REFIT_PAIR) against the one-wave form, element by element (development):
 the packed operator incl. the inverted diagonal blocks, relative to its largest element."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -7,6 +7,7 @@ import torch
 from bayesian_cbf_amd import ops
 from bayesian_cbf_amd.synthetic import make_instances
 ok = True
+FORMS = {"0": ops.REFIT_WAVE, "1": ops.REFIT_PAIR}
 for DT in (torch.float64, torch.float32):
     for Bt, N, n, m in ((64, 32, 2, 1), (64, 64, 2, 1), (300, 100, 3, 2), (1024, 256, 2, 1), (130, 250, 4, 2), (256, 512, 3, 2), (70, 40, 6, 3)):
         p = make_instances(Bt, N, n, m, dtype=DT, device="cuda", seed=7)
@@ -14,8 +15,7 @@ for DT in (torch.float64, torch.float32):
             p["jitter"][::7] = -1.0
         out = {}
         for form in ("0", "1"):
-            os.environ["BCBF_REFIT_WAVE"] = "1"; os.environ["BCBF_REFIT_PAIR"] = form
-            Lop, UHB, info = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])[:3]
+            Lop, UHB, info = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"], form=FORMS[form])[:3]
             torch.cuda.synchronize()
             out[form] = (Lop.clone(), UHB.clone(), info.clone())
         good = out["0"][2] == 0
@@ -34,8 +34,7 @@ for Bt, N, n, m in ((256, 64, 2, 1), (256, 256, 2, 1), (128, 512, 3, 2)):
     xq = p["X"][:, 0, :].contiguous() + 0.1
     res = {}
     for form, q in (("ref64", {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in p.items()}), ("0", p), ("1", p)):
-        os.environ["BCBF_REFIT_WAVE"] = "1"; os.environ["BCBF_REFIT_PAIR"] = "0" if form == "ref64" else form
-        Lop, UHB, info = ops.refit(q["X"], q["UH"], q["Bm"], q["ell"], q["s2"], q["jitter"])[:3]
+        Lop, UHB, info = ops.refit(q["X"], q["UH"], q["Bm"], q["ell"], q["s2"], q["jitter"], form=FORMS["0" if form == "ref64" else form])[:3]
         Vw = ops.potrs(Lop, q["Xdot"], q["UH"], q["M0"], want_alpha=False)
         Vw = Vw[0] if isinstance(Vw, tuple) else Vw
         Mk, Bk = ops.posterior_step(Lop, Vw, q["X"], UHB, q["ell"], q["s2"], q["Bm"], q["M0"], xq.to(q["X"].dtype))[:2]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The team-of-waves form of the refit (BCBF_REFIT_TEAM=1) against the library's default choice without it, element by
+"""The team-of-waves form of the refit (form=REFIT_TEAM8) against the one-wave form, element by
 element, and its time against the other forms for a few large systems (development)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))); sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,18 +7,15 @@ import torch
 from _timing import timeit
 from bayesian_cbf_amd import ops
 from bayesian_cbf_amd.synthetic import make_instances
-def run(p, env):
-    for k in ("BCBF_REFIT_TEAM", "BCBF_REFIT_WAVE", "BCBF_REFIT_PAIR"):
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    return ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])[:3]
+def run(p, form):
+    return ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"], form=form)[:3]
 ok = True
 for DT in (torch.float64, torch.float32):
     for Bt, N, n, m in ((1, 512, 3, 2), (3, 500, 2, 1), (5, 700, 6, 3), (2, 1024, 3, 2), (1, 2048, 3, 2), (4, 40, 2, 1), (2, 100, 3, 2)):
         p = make_instances(Bt, N, n, m, dtype=DT, device="cuda", seed=21)
         if Bt >= 3:
             p["jitter"][1, N // 2] = -1.0                         # a failed pivot in one instance
-        a = run(p, {"BCBF_REFIT_TEAM": "1"}); b = run(p, {"BCBF_REFIT_TEAM": "0"})
+        a = run(p, ops.REFIT_TEAM8); b = run(p, ops.REFIT_WAVE)
         torch.cuda.synchronize()
         good = b[2] == 0
         same = bool((a[2] == b[2]).all())
@@ -33,6 +30,6 @@ for DT in (torch.float64, torch.float32):
                 continue
             p = make_instances(Bt, N, 3, 2, dtype=DT, device="cuda", seed=5)
             t = {}
-            for name, env in (("team", {"BCBF_REFIT_TEAM": "1"}), ("workgroup", {"BCBF_REFIT_WAVE": "0", "BCBF_REFIT_PAIR": "0"}), ("wave", {"BCBF_REFIT_WAVE": "1", "BCBF_REFIT_PAIR": "0"})):
-                t[name] = timeit(lambda: run(p, env), reps=5)
+            for name, form in (("team", ops.REFIT_TEAM8), ("workgroup", ops.REFIT_WORKGROUP), ("wave", ops.REFIT_WAVE)):
+                t[name] = timeit(lambda: run(p, form), reps=5)
             print(str(DT)[6:], "N", N, "batch", Bt, " ".join("%s %.3f" % kv for kv in t.items()))

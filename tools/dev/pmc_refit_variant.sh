@@ -3,13 +3,14 @@
 LIB=$1; OCC=$2; TAG=$3
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-export BCBF_LIB_PATH=$LIB BCBF_RW32_OCC=$OCC BCBF_REFIT_WAVE=1
+export BCBF_LIB_PATH=$LIB
+FORM=$((2 + 64 * OCC))      # ops.REFIT_WAVE | REFIT_OCC1 / REFIT_OCC2
 O=gpurun_out/pmcv_$TAG
 mkdir -p $O
 for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   d=$O/$(echo $c | tr ' ' '_')
   rm -rf $d
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -- python3 tools/refit_only.py f32 4096 512 6 > $d.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -- python3 tools/refit_only.py f32 4096 512 6 $FORM > $d.log 2>&1
 done
 python3 - <<PY
 import csv, glob, json

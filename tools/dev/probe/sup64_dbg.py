@@ -3,14 +3,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirna
 if len(sys.argv) > 1:
     from bayesian_cbf_amd import ops
     from bayesian_cbf_amd.synthetic import make_instances
-    os.environ["BCBF_REFIT_WAVE"] = "1"
     p = make_instances(4, 1024, 3, 2, dtype=torch.float64, device="cuda", seed=5)
-    Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])
+    Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"],
+                                 form=ops.REFIT_WAVE | (ops.REFIT_SUPER_OFF if "plain" in sys.argv else ops.REFIT_SUPER_ON))
     np.save(sys.argv[1], Lop[0].cpu().numpy())
     print("info", info.tolist())
 else:
     subprocess.run([sys.executable, __file__, "/tmp/a.npy"])
-    subprocess.run([sys.executable, __file__, "/tmp/b.npy"], env=dict(os.environ, BCBF_RW64_SUPER_FORCE="0"))
+    subprocess.run([sys.executable, __file__, "/tmp/b.npy", "plain"])
     a, b = np.load("/tmp/a.npy"), np.load("/tmp/b.npy")
     Np = 1024
     bad = np.nonzero(~(np.abs(a - b) <= 1e-9 * (1 + np.abs(b))))[0]

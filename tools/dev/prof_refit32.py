@@ -3,7 +3,6 @@
    build: bash tools/build_variant.sh prof refit_wave64.hip -DBCBF_RW64_PROF      run (GPU box): python tools/dev/prof_refit32.py"""
 import os, sys, json
 os.environ["BCBF_LIB_PATH"] = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "_variants", "libbcbf_prof.so")
-os.environ["BCBF_REFIT_WAVE"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from bayesian_cbf_amd import ops
@@ -13,14 +12,14 @@ for Bt, N in ((1024, 512), (4096, 512), (1024, 1024)):
     p = make_instances(Bt, N, 3, 2, dtype=torch.float32, device="cuda", seed=5)
     for sup in ("0", "1"):
         for occ in ("1", "2"):
-            os.environ["BCBF_RW32_SUPER_FORCE"], os.environ["BCBF_RW32_OCC"] = sup, occ
+            FORM = ops.REFIT_WAVE | (ops.REFIT_SUPER_ON if sup == "1" else ops.REFIT_SUPER_OFF) | (ops.REFIT_OCC2 if occ == "2" else ops.REFIT_OCC1)
             for _ in range(3):
-                Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])
+                Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"], form=FORM)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(5):
-                Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])
+                Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"], form=FORM)
             e1.record()
             torch.cuda.synchronize()
             Np = (N + 31) // 32 * 32

@@ -25,7 +25,7 @@ def build():
         out = os.path.join(VDIR, name + ".so")
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + flags + [
-               os.path.join(CSRC, f) for f in ("refit_wave64.hip", "refit_mfma64.hip", "common.hip")] + ["-o", out]
+               os.path.join(CSRC, f) for f in ("refit.hip", "refit_wave64.hip", "refit_mfma.hip", "refit_mfma64.hip", "common.hip")] + ["-o", out]
         procs.append((name, subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True)))
     for name, p in procs:
         _, err = p.communicate()
@@ -39,7 +39,6 @@ def run():
     import torch
     sys.path.insert(0, ROOT)
     from bayesian_cbf_amd.synthetic import make_instances
-    os.environ["BCBF_REFIT_WAVE"] = "1"
     P = ctypes.c_void_p
     shapes = [(1024, 256, 2, 1), (4096, 256, 2, 1), (4096, 512, 3, 2)]
     data = {}
@@ -56,12 +55,12 @@ def run():
         if not os.path.exists(path):
             continue
         lib = ctypes.CDLL(path)
-        fn = lib.bcbf_refit_mfma_f64
+        fn = lib.bcbf_refit_form_f64
         fn.restype = ctypes.c_int
         for (Bt, N, n, m), (p, Lop, UHB, Ld, info) in data.items():
             prof = name.endswith("_prof")
             args = [P(p[k].data_ptr()) for k in ("X", "UH", "Bm", "ell", "s2", "jitter")] + [None, P(Lop.data_ptr()), P(UHB.data_ptr()),
-                    P(Ld.data_ptr()) if (prof and Ld is not None) else None, P(info.data_ptr()), Bt, N, n, m, None]
+                    P(Ld.data_ptr()) if (prof and Ld is not None) else None, None, P(info.data_ptr()), Bt, N, n, m, 0, 2, None]   # form 2: one wave per instance
             for _ in range(2):
                 rc = fn(*args)
             torch.cuda.synchronize()

@@ -4,6 +4,6 @@ cd $GRAFT_REPO_ROOT
 for lib in bayesian_cbf_amd/libbcbf.so tools/_variants/libbcbf_*.so; do
   for occ in 1 2; do
     echo "== $lib occ=$occ"
-    BCBF_LIB_PATH=$lib BCBF_RW32_OCC=$occ BCBF_REFIT_WAVE=1 python tools/dev/time_refit32.py 2>&1 | tail -3
+    BCBF_LIB_PATH=$lib python tools/dev/time_refit32.py "" $occ 2>&1 | tail -3
   done
 done

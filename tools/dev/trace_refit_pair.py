@@ -13,11 +13,10 @@ from bayesian_cbf_amd.synthetic import make_instances
 DT = torch.float32 if (len(sys.argv) > 1 and sys.argv[1] == "f32") else torch.float64
 Bt = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 256
-os.environ["BCBF_REFIT_WAVE"] = "1"; os.environ["BCBF_REFIT_PAIR"] = "1"
 n, m = (2, 1) if N <= 256 else (3, 2)
 p = make_instances(Bt, N, n, m, dtype=DT, device="cuda", seed=5)
 for _ in range(20):
-    ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"])
+    ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], p["jitter"], form=ops.REFIT_PAIR)
 torch.cuda.synchronize()
 buf = np.zeros((2, 4096), dtype=np.int64)
 rc = _lib.lib.bcbf_debug_rp_trace(ctypes.c_void_p(buf.ctypes.data)); assert rc == 0

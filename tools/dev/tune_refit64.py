@@ -12,7 +12,7 @@ def build():
     ps = []
     for name, fl in VARIANTS.items():
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"),
-               "-I" + CSRC] + fl + [os.path.join(CSRC, "refit_mfma64.hip"), os.path.join(CSRC, "common.hip"), "-o", os.path.join(VDIR, "r64_" + name + ".so")]
+               "-I" + CSRC] + fl + [os.path.join(CSRC, f) for f in ("refit.hip", "refit_mfma.hip", "refit_mfma64.hip", "refit_wave64.hip", "common.hip")] + ["-o", os.path.join(VDIR, "r64_" + name + ".so")]
         ps.append(subprocess.Popen(cmd, stderr=subprocess.DEVNULL))
         if len(ps) >= 6:
             assert all(p.wait() == 0 for p in ps); ps = []
@@ -32,8 +32,8 @@ def run():
         for name in VARIANTS:
             lib = ctypes.CDLL(os.path.join(VDIR, "r64_" + name + ".so"))
             def call():
-                rc = lib.bcbf_refit_mfma_f64(q(p["X"]), q(p["UH"]), q(p["Bm"]), q(p["ell"]), q(p["s2"]), q(p["jitter"]), None, q(Lop), q(UHB), None, q(info),
-                                             Bt, N, n, m, P(torch.cuda.current_stream().cuda_stream)); assert rc == 0
+                rc = lib.bcbf_refit_form_f64(q(p["X"]), q(p["UH"]), q(p["Bm"]), q(p["ell"]), q(p["s2"]), q(p["jitter"]), None, q(Lop), q(UHB), None, None, q(info),
+                                             Bt, N, n, m, 0, ops.REFIT_WORKGROUP, P(torch.cuda.current_stream().cuda_stream)); assert rc == 0
             call(); torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()

@@ -26,19 +26,12 @@ while done < launches:
     jit = p["jitter"].clone()
     for _ in range(int(rng.integers(0, 4))):                      # failed pivots at random places in random instances
         jit[int(rng.integers(Bt)), int(rng.integers(N))] = -10.0
-    form = rng.choice(["default", "pair", "team8", "team4", "wave"])
-    for k in ("BCBF_REFIT_TEAM", "BCBF_REFIT_WAVE", "BCBF_REFIT_PAIR"):
-        os.environ.pop(k, None)
-    if form == "pair" and N <= 512:
-        os.environ["BCBF_REFIT_WAVE"] = "1"; os.environ["BCBF_REFIT_PAIR"] = "1"
-    elif form == "team8":
-        os.environ["BCBF_REFIT_TEAM"] = "18"
-    elif form == "team4":
-        os.environ["BCBF_REFIT_TEAM"] = "14"
-    elif form == "wave":
-        os.environ["BCBF_REFIT_WAVE"] = "1"; os.environ["BCBF_REFIT_PAIR"] = "0"
+    form = [None, ops.REFIT_PAIR, ops.REFIT_TEAM8, ops.REFIT_TEAM4, ops.REFIT_WAVE][int(rng.integers(5))]
+    if form == ops.REFIT_PAIR and N > 512:
+        form = None
     for rep in range(int(rng.integers(1, 6))):
-        Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], jit, want_dense=bool(rng.random() < 0.15 and N <= 300))
+        Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], jit, want_dense=bool(rng.random() < 0.15 and N <= 300),
+                                      form=form)
         torch.cuda.synchronize()
         done += 1
 print("ok: %d launches in %.1f s" % (done, time.time() - t0))
