@@ -134,6 +134,12 @@ _TSIGS = {
     "bcbf_pendulum_clf_cbf_control": [P, P, c_int, "T", "PT", "T", "T", "T", c_int, "T"] + [P] * 6 + [c_int, P],
     "bcbf_pendulum_clf_cbf_rollout": [P, P, c_int, P, c_int, "T", "PT", "T", "T", "T", c_int, "T", "T"] + [P] * 5
                                      + [c_int] * 4 + [P],
+    # the unicycle's CLF-CBF program on the mean model: lo, hi, Kp, tw, gammas are HOST pointers
+    "bcbf_clf_cbf_qp2": [P, P, "PT", "PT", "T", P, P, P, P, c_int, c_int, P],
+    "bcbf_unicycle_clf_cbf_control": [P, P, P, "PT", c_int, "T", "T", "PT", "PT", P, c_int, P, P, c_int, "PT", "PT"] + [P] * 7
+                                     + [c_int, c_int, P],
+    "bcbf_unicycle_clf_cbf_rollout": [P, P, P, c_int, c_int, c_int, c_int, "PT", c_int, "T", "T", "PT", "PT", P, c_int, P, c_int,
+                                      P, P, c_int, "PT", "PT", "T", "T"] + [P] * 6 + [c_int] * 5 + [P],
     # LQRController.control (controllers.py:64-115) and the two bdlqr LinearSystem solves inside it; x_goal, Q, R: HOST values
     "bcbf_lqr_nominal": [P, P, P, "PT", "PT", "PT", "T", c_int, c_int, P, P, P, P, c_int, c_int, c_int, P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],

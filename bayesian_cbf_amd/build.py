@@ -21,7 +21,7 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libbcbf.so")
 ARCH = "gfx950"
 SOURCES = ["common.hip", "posterior_step.hip", "jets_mfma.hip", "posterior_shared.hip", "posterior_shared_reg.hip", "refit.hip", "refit_mfma.hip", "refit_mfma64.hip", "refit_wave64.hip", "solve.hip", "trtri.hip", "tail.hip", "syrk.hip", "mll_grad.hip", "fit.hip", "cbc_terms.hip", "predict_assemble.hip", "gram.hip", "controller_cones.hip", "socp.hip", "socp_quad.hip",
-           "unicycle.hip", "control_step.hip", "subsample.hip", "pendulum.hip", "trigger.hip", "trigger_step.hip", "pendulum_qp.hip", "lqr.hip"]
+           "unicycle.hip", "control_step.hip", "subsample.hip", "pendulum.hip", "trigger.hip", "trigger_step.hip", "pendulum_qp.hip", "lqr.hip", "unicycle_qp.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
          "-I" + CSRC, "-Wall", "-Wno-unused-function", "-fvisibility=hidden"]
 # per-file extras.  posterior_shared: MFMA results are consumed by VALU code every block, so keep the accumulators
@@ -33,6 +33,7 @@ EXTRA_FLAGS = {"posterior_shared.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "posterior_shared_reg.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "posterior_step.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "pendulum_qp.hip": ["-Rpass-analysis=kernel-resource-usage"],
+               "unicycle_qp.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "pendulum.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 # instantiations of the streaming kernel whose measured figures assume ZERO scratch (a spill in the streaming loop is fatal
 # there: DESIGN.md 3.1 -- 1373 us against 470): the headline (fp32 / fp64 values-only, C = 2..3), the fp32 jets of the pendulum and
@@ -47,6 +48,9 @@ ZERO_SCRATCH_KERNELS = {"posterior_step.hip": [
     "posterior_step_kernel<double, 4, 4, 0, 1, false, 0,", "posterior_step_kernel<double, 3, 8, 0, 1, false, 0,"],
     # the in-kernel closed loop keeps state, parameters and statistics in registers for all of its steps
     "pendulum_qp.hip": ["pendulum_clf_cbf_rollout_kernel<float>", "pendulum_clf_cbf_rollout_kernel<double>"],
+    # the unicycle's: row arrays indexed by compile-time constants only, per number of obstacles (and the polar CLF)
+    "unicycle_qp.hip": ["unicycle_clf_cbf_rollout_kernel<%s, %s>" % (t, k) for t in ("float", "double")
+                        for k in ("0, false", "1, false", "2, false", "3, false", "0, true")],
     # the posterior-drawn plant: two Cholesky factors, the draw and the condition live in registers (every index a constant)
     "pendulum.hip": ["pendulum_sampled_plant_kernel<double>"]}
 # kernels that must not touch scratch memory (posterior_shared_reg: an operand spilled between its explicit LDS read and

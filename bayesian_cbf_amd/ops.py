@@ -1951,3 +1951,178 @@ def pendulum_clf_cbf_rollout(x, min_h, damage, status, numSteps, dt=0.002, ctrl_
         _p(x), _p(cm), cs, _p(tm), ts, *task, dt, _p(min_h), _p(damage), _p(status), _p(traj), _p(u_rec), record_every,
         t_offset, numSteps, Bt, _stream(x)), "bcbf_pendulum_clf_cbf_rollout")
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The unicycle's CLF-CBF quadratic program on the mean model (bcbf_clf_cbf_qp2 / bcbf_unicycle_clf_cbf_control / _rollout):
+# ControllerCLF, the controller the Bayesian one is measured against.  fp32 and fp64.
+_UNICYCLE_CLF_KINDS = {"cartesian": 0, "polar": 1, 0: 0, 1: 1}
+_UNICYCLE_PLANNER_KINDS = {"none": 0, "piecewise": 1, 0: 0, 1: 1}
+UNICYCLE_CTRL_MIN, UNICYCLE_CTRL_MAX = (-10.0, -5 * math.pi), (10.0, 5 * math.pi)
+
+
+def _host(like, values, n, what):
+    """A host array of the tensor's precision (the library's HOST-pointer arguments)."""
+    ct = ctypes.c_float if like.dtype == torch.float32 else ctypes.c_double
+    values = [float(v) for v in (values.tolist() if torch.is_tensor(values) else values)]
+    if len(values) != n:
+        raise ValueError("%s must have %d values, got %d" % (what, n, len(values)))
+    return (ct * max(n, 1))(*values)
+
+
+def _unicycle_scalar_rows(v, Bt, like, what):
+    """(tensor, stride) of a wheelbase for the library: a number or a tensor[1] is shared (stride 0), a tensor[Bt] one value
+    per instance (stride 1)."""
+    if not torch.is_tensor(v):
+        v = torch.tensor([float(v)], dtype=like.dtype, device=like.device)
+    if v.dtype != like.dtype or v.device != like.device or not v.is_contiguous():
+        raise TypeError("%s must be a contiguous %s tensor on %s" % (what, like.dtype, like.device))
+    if v.numel() == 1 and v.ndim <= 1:
+        return v.reshape(1), 0
+    if tuple(v.shape) == (Bt,):
+        return v, 1
+    raise ValueError("%s must be a number, a tensor[1] or a tensor[Bt]; got %s" % (what, tuple(v.shape)))
+
+
+def _unicycle_obstacles(centers, radii, Bt, like):
+    """(centers, radii, stride, Kob): centers[Kob,2] / radii[Kob] shared (stride 0) or centers[Bt,Kob,2] / radii[Bt,Kob] per
+    instance (stride 1); None: no obstacles."""
+    if centers is None or radii is None:
+        if centers is not None or radii is not None:
+            raise ValueError("centers and radii come together")
+        return None, None, 0, 0
+    for name, t in (("centers", centers), ("radii", radii)):
+        if t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
+            raise TypeError("%s must be a contiguous %s tensor on %s" % (name, like.dtype, like.device))
+    if centers.ndim == 2 and centers.shape[1] == 2 and tuple(radii.shape) == (centers.shape[0],):
+        return centers, radii, 0, centers.shape[0]
+    if centers.ndim == 3 and centers.shape[0] == Bt and centers.shape[2] == 2 and tuple(radii.shape) == tuple(centers.shape[:2]):
+        return centers, radii, 1, centers.shape[1]
+    raise ValueError("obstacles must be centers[Kob,2] / radii[Kob] or centers[Bt,Kob,2] / radii[Bt,Kob]; got %s / %s"
+                     % (tuple(centers.shape), tuple(radii.shape)))
+
+
+def _unicycle_qp_task(x, Kp, clf_kind, clf_gamma, relax_weight, lo, hi, L_ctrl, centers, radii, tw, gammas):
+    """The task arguments of the control / rollout entries from `Kp` to `gammas`, in the library's order, and Kob."""
+    Bt = x.shape[0]
+    try:
+        kind = _UNICYCLE_CLF_KINDS[clf_kind]
+    except KeyError:
+        raise ValueError("clf_kind must be 'cartesian' (0) or 'polar' (1), got %r" % (clf_kind,))
+    Kp = list(Kp.tolist() if torch.is_tensor(Kp) else Kp)
+    Kp = Kp + [0.0] * (4 - len(Kp))                      # CLFCartesian has three gains
+    Lc, Ls = _unicycle_scalar_rows(L_ctrl, Bt, x, "L_ctrl")
+    centers, radii, ostride, Kob = _unicycle_obstacles(centers, radii, Bt, x)
+    gam = list(gammas.tolist() if torch.is_tensor(gammas) else gammas) if Kob else []
+    args = [_host(x, Kp, 4, "Kp"), kind, clf_gamma, relax_weight, _host(x, lo, 2, "lo"), _host(x, hi, 2, "hi"), _p(Lc), Ls,
+            _p(centers), _p(radii), ostride, _host(x, tw, 2, "tw") if Kob else None,
+            _host(x, gam, Kob, "gammas") if Kob else None]
+    return args, Kob, (Lc, centers, radii)
+
+
+def clf_cbf_qp2(a, b, lo=UNICYCLE_CTRL_MIN, hi=UNICYCLE_CTRL_MAX, relax_weight=10.0, want=("u", "relax", "active", "status")):
+    """The program  min |u|^2 + relax_weight relax  s.t.  lo <= u <= hi,  a[:,0].u + b[:,0] - relax <= 0,  a[:,k].u + b[:,k] >= 0
+    (k >= 1)  for a batch: a[Bt,K,2], b[Bt,K], 1 <= K <= 4.  The unique optimum in closed form (projection of
+    -(relax_weight/2) a_0 onto the polygon, active sets of size <= 2 enumerated).
+    Returns dict(u[Bt,2], relax[Bt], active[Bt] (int32 bitmask over lo0, lo1, hi0, hi1, hard rows), status[Bt]) of the outputs
+    named in `want`; status 1 = infeasible (u, relax are then NaN and active -1: the library leaves them unwritten)."""
+    _chk(a, b)
+    if a.ndim != 3 or a.shape[2] != 2 or tuple(b.shape) != tuple(a.shape[:2]):
+        raise ValueError("a must be [Bt,K,2] and b [Bt,K]")
+    Bt, K = b.shape
+    out = _unicycle_qp_outputs(a, Bt, want)
+    check(getattr(lib, "bcbf_clf_cbf_qp2" + _suf(a))(
+        _p(a), _p(b), _host(a, lo, 2, "lo"), _host(a, hi, 2, "hi"), relax_weight, _p(out.get("u")), _p(out.get("relax")),
+        _p(out.get("active")), _p(out.get("status")), Bt, K, _stream(a)), "bcbf_clf_cbf_qp2")
+    return out
+
+
+def _unicycle_qp_outputs(like, Bt, want, K=None):
+    f = dict(dtype=like.dtype, device=like.device)
+    make = dict(a=lambda: torch.empty(Bt, K, 2, **f), b=lambda: torch.empty(Bt, K, **f), values=lambda: torch.empty(Bt, K, **f),
+                u=lambda: torch.full((Bt, 2), float("nan"), **f), relax=lambda: torch.full((Bt,), float("nan"), **f),
+                active=lambda: torch.full((Bt,), -1, dtype=torch.int32, device=like.device),
+                status=lambda: torch.zeros(Bt, dtype=torch.int32, device=like.device))
+    unknown = [w for w in want if w not in make or (K is None and w in ("a", "b", "values"))]
+    if unknown:
+        raise ValueError("unknown outputs %s" % unknown)
+    return {w: make[w]() for w in want}
+
+
+def unicycle_clf_cbf_control(x, plan, dot_plan, Kp=(0.9, 1.5, 4.0), clf_kind="cartesian", clf_gamma=10.0, relax_weight=10.0,
+                             lo=UNICYCLE_CTRL_MIN, hi=UNICYCLE_CTRL_MAX, L_ctrl=1.0, centers=None, radii=None, tw=(0.5, 0.5),
+                             gammas=(), want=("a", "b", "values", "u", "relax", "active", "status")):
+    """One evaluation of the unicycle's mean-model CLF-CBF controller (ControllerCLF.control) for a batch of states x[Bt,3]
+    with plan[Bt,3], dot_plan[Bt,3]: the rows of CLFCartesian + ObstacleCBF on AckermannDrive(L_ctrl) (clf_kind 'cartesian')
+    or of CLFPolar on PolarDynamics through cartesian2polar ('polar', no obstacles), and the optimum of the program in closed
+    form.  L_ctrl: a number or a tensor[Bt]; obstacles: centers[Kob,2] / radii[Kob] shared or [Bt,Kob,2] / [Bt,Kob] per instance.
+    Returns dict(a[Bt,1+Kob,2], b[Bt,1+Kob], values[Bt,1+Kob] = (V, h_k), u[Bt,2], relax[Bt], active[Bt], status[Bt]) of the
+    outputs named in `want`; status 1 = infeasible (u, relax NaN, active -1)."""
+    _chk(x, plan, dot_plan)
+    Bt = x.shape[0]
+    if x.ndim != 2 or x.shape[1] != 3 or tuple(plan.shape) != (Bt, 3) or tuple(dot_plan.shape) != (Bt, 3):
+        raise ValueError("x, plan and dot_plan must be [Bt,3]")
+    task, Kob, keep = _unicycle_qp_task(x, Kp, clf_kind, clf_gamma, relax_weight, lo, hi, L_ctrl, centers, radii, tw, gammas)
+    out = _unicycle_qp_outputs(x, Bt, want, 1 + Kob)
+    check(getattr(lib, "bcbf_unicycle_clf_cbf_control" + _suf(x))(
+        _p(x), _p(plan), _p(dot_plan), *task, _p(out.get("a")), _p(out.get("b")), _p(out.get("values")), _p(out.get("u")),
+        _p(out.get("relax")), _p(out.get("active")), _p(out.get("status")), Bt, Kob, _stream(x)),
+        "bcbf_unicycle_clf_cbf_control")
+    return out
+
+
+def unicycle_clf_cbf_records(t_offset, numSteps, record_every):
+    """How many of the global steps t_offset .. t_offset + numSteps - 1 are multiples of record_every (0: none recorded)."""
+    return pendulum_clf_cbf_records(t_offset, numSteps, record_every)
+
+
+def unicycle_planner_steps(numStepsPlan, frac_time_to_reach_goal=0.7):
+    """(t2, lookahead) of PiecewiseLinearPlanner(numStepsPlan, ., frac) as planner.py computes them: the integers the
+    rollout entry takes from the host."""
+    return min(int(numStepsPlan * frac_time_to_reach_goal), numStepsPlan - 1), max(int(0.1 * numStepsPlan), 1)
+
+
+def unicycle_clf_cbf_rollout(x, goal, cost, status, numSteps, dt=0.05, min_h=None, converged_at=None, planner="none",
+                             x0_plan=None, numStepsPlan=0, frac_time_to_reach_goal=0.7, Kp=(0.9, 1.5, 4.0),
+                             clf_kind="cartesian", clf_gamma=10.0, relax_weight=10.0, lo=UNICYCLE_CTRL_MIN,
+                             hi=UNICYCLE_CTRL_MAX, L_ctrl=1.0, L_true=None, centers=None, radii=None, tw=(0.5, 0.5), gammas=(),
+                             stop_rho=0.0, traj=None, u_rec=None, record_every=0, t_offset=0):
+    """numSteps steps of the closed loop (controller of `unicycle_clf_cbf_control` on L_ctrl, explicit Euler on the plant's
+    wheelbase L_true -- None: the controller's) for every instance in ONE launch.  planner 'none': plan = goal[Bt,3];
+    'piecewise': PiecewiseLinearPlanner(x0_plan[Bt,3], goal, numStepsPlan, dt, frac_time_to_reach_goal) evaluated inside the
+    kernel at the global step.  In place: x[Bt,3], min_h[Bt] (needed with obstacles), cost[Bt] (sum |u|^2), status[Bt] (int32;
+    the 1-based global step at which an instance's program became infeasible -- it is frozen from there on), converged_at[Bt]
+    (int32, -1 = running; needed with stop_rho > 0: the global step before which |goal - x| < stop_rho, the instance stops
+    there).  Calls compose bit for bit (the second with t_offset = the steps done).  traj[r,Bt,3] / u_rec[r,Bt,2]: (x_t, u_t)
+    of the global steps that are multiples of record_every, this call's first at row 0;
+    r = unicycle_clf_cbf_records(t_offset, numSteps, record_every).  Returns x."""
+    _chk(x, goal, cost, status, min_h, converged_at, x0_plan, traj, u_rec)
+    Bt = x.shape[0]
+    if x.ndim != 2 or x.shape[1] != 3 or tuple(goal.shape) != (Bt, 3) or goal.dtype != x.dtype:
+        raise ValueError("x and goal must be [Bt,3] of the same dtype")
+    for name, t in (("cost", cost), ("min_h", min_h)):
+        if t is not None and (tuple(t.shape) != (Bt,) or t.dtype != x.dtype):
+            raise ValueError("%s must be a %s tensor [Bt]" % (name, x.dtype))
+    for name, t in (("status", status), ("converged_at", converged_at)):
+        if t is not None and (tuple(t.shape) != (Bt,) or t.dtype != torch.int32):
+            raise ValueError("%s must be an int32 tensor [Bt]" % name)
+    try:
+        pkind = _UNICYCLE_PLANNER_KINDS[planner]
+    except KeyError:
+        raise ValueError("planner must be 'none' (0) or 'piecewise' (1), got %r" % (planner,))
+    t2 = look = 0
+    if pkind == 1:
+        if x0_plan is None or tuple(x0_plan.shape) != (Bt, 3) or x0_plan.dtype != x.dtype:
+            raise ValueError("planner 'piecewise' needs x0_plan [Bt,3]")
+        t2, look = unicycle_planner_steps(int(numStepsPlan), frac_time_to_reach_goal)
+    task, Kob, keep = _unicycle_qp_task(x, Kp, clf_kind, clf_gamma, relax_weight, lo, hi, L_ctrl, centers, radii, tw, gammas)
+    Lt, Lts = (keep[0], task[7]) if L_true is None else _unicycle_scalar_rows(L_true, Bt, x, "L_true")
+    nrec = unicycle_clf_cbf_records(t_offset, numSteps, record_every)
+    for name, t, shape in (("traj", traj, (Bt, 3)), ("u_rec", u_rec, (Bt, 2))):
+        if t is not None and (t.dtype != x.dtype or tuple(t.shape[1:]) != shape or t.shape[0] < nrec):
+            raise ValueError("%s must be a %s tensor [>= %d, %s]" % (name, x.dtype, nrec, ", ".join(map(str, shape))))
+    check(getattr(lib, "bcbf_unicycle_clf_cbf_rollout" + _suf(x))(
+        _p(x), _p(goal), _p(x0_plan), pkind, t2, look, int(numStepsPlan), *task[:8], _p(Lt), Lts, *task[8:], dt, stop_rho,
+        _p(min_h), _p(cost), _p(status), _p(converged_at), _p(traj), _p(u_rec), record_every, t_offset, numSteps, Bt, Kob,
+        _stream(x)), "bcbf_unicycle_clf_cbf_rollout")
+    return x

@@ -1888,3 +1888,78 @@ def pendulum_clf_cbf_rollouts(Bt, numSteps=15000, dt=0.002, theta0=5 * math.pi /
     stats = reduce_rollout_stats(collided.sum(), min_h.min(), 0.0, fails.sum(), Bt)
     return dict(stats=stats, x_final=x, min_h=min_h, fails=fails, damage=damage, status=status, traj=traj, u=us,
                 loop_seconds=t_loop)
+
+
+def unicycle_clf_cbf_rollouts(Bt, numSteps=200, dt=0.05, L_ctrl=1.0, L_true=12.0, start=(-3.0, -1.0, -math.pi / 4),
+                              goal=(0.0, 0.0, math.pi / 4), start_noise=(0.3, 0.3, 0.5), planner="piecewise", clf="cartesian",
+                              obstacles="mid", record_every=0, steps_per_launch=None, dtype=torch.float64, device="cuda", seed=0,
+                              Kp=None, term_weights=(0.7, 0.3), cbf_gammas=(5.0, 5.0), frac_time_to_reach_goal=0.95,
+                              stop_rho=0.0, x0=None):
+    """Bt closed loops of the unicycle's CLF-CBF quadratic program on the MEAN model (ControllerCLF, the controller of the
+    reference's model-based demos) from perturbed starts, every step of every loop inside the library's rollout kernel
+    (bcbf_unicycle_clf_cbf_rollout): one launch, or ceil(numSteps / steps_per_launch) launches that compose bit for bit.
+
+    L_ctrl: the wheelbase the controller believes.  L_true: the plant's -- a number or a tensor[Bt] (one plant per instance):
+    a plant that differs from the controller's model is the model-mismatch study (the defaults are those of
+    unicycle_mean_cbf_collides_obstacle: 1 against 12).  planner 'piecewise': PiecewiseLinearPlanner(start, goal, numSteps, dt,
+    frac_time_to_reach_goal) -- ONE plan from the nominal start for every instance, as the Monte-Carlo drivers do -- with
+    Kp = (0.9, 1.5, 0) (track_trajectory_clf_cartesian); 'none': the goal itself, Kp = (0.9, 1.5, 4).  clf 'polar': CLFPolar
+    through cartesian2polar (Kp = (0.6, 1.5, 4, 0); no obstacles, planner 'none').  obstacles 'mid':
+    obstacles_at_mid_from_start_and_goal(start, goal, term_weights) with cbf_gammas; None: none.  stop_rho > 0: an instance
+    stops once it is within stop_rho of the goal (`converged_at` = that step, -1 = still running).  x0: explicit starts [Bt,3].
+    A trajectory collides when min_h < 0 (NaN-safe: anything not provably >= 0 counts); an instance whose program became
+    infeasible is frozen at that step (`status` = its 1-based step) and contributes the statistics it had until then.
+    Returns dict(stats (`reduce_rollout_stats`), x_final[Bt,3], min_h[Bt], cost[Bt] (sum |u|^2), status[Bt], converged_at[Bt],
+    dist_to_goal[Bt], traj[nrec,Bt,3] and u[nrec,Bt,2] (record_every > 0: the steps that are multiples of it, before the step),
+    loop_seconds)."""
+    from .unicycle_move_to_pose import obstacles_at_mid_from_start_and_goal
+    dev = torch.device(device)
+    f = dict(dtype=dtype, device=dev)
+    start_t, goal_t = torch.tensor([float(v) for v in start], **f), torch.tensor([float(v) for v in goal], **f)
+    if x0 is None:
+        gen = torch.Generator(device=dev).manual_seed(seed)
+        x = (start_t + torch.tensor([float(v) for v in start_noise], **f) * torch.randn(Bt, 3, generator=gen, **f)).contiguous()
+    else:
+        x = torch.as_tensor(x0).to(**f).reshape(Bt, 3).clone().contiguous()
+    if clf == "polar" and (obstacles is not None or planner != "none"):
+        raise ValueError("clf='polar' runs with planner='none' and obstacles=None")
+    if Kp is None:
+        Kp = (0.6, 1.5, 4.0, 0.0) if clf == "polar" else (0.9, 1.5, 0.0) if planner == "piecewise" else (0.9, 1.5, 4.0)
+    kw = dict(Kp=Kp, clf_kind=clf, L_ctrl=L_ctrl, L_true=L_true.to(**f).contiguous() if torch.is_tensor(L_true) else L_true,
+              planner=planner, stop_rho=stop_rho)
+    if planner == "piecewise":
+        kw.update(x0_plan=start_t.expand(Bt, 3).contiguous(), numStepsPlan=numSteps, frac_time_to_reach_goal=frac_time_to_reach_goal)
+    if obstacles == "mid":
+        obs = obstacles_at_mid_from_start_and_goal(start_t, goal_t, term_weights=tuple(term_weights))
+        kw.update(centers=torch.stack([o.center.to(**f) for o in obs]).contiguous(),
+                  radii=torch.stack([o.radius.to(**f) for o in obs]).contiguous(), tw=tuple(term_weights), gammas=tuple(cbf_gammas))
+    elif obstacles is not None:
+        raise ValueError("obstacles must be 'mid' or None, got %r" % (obstacles,))
+    goal_b = goal_t.expand(Bt, 3).contiguous()
+    min_h, cost = torch.full((Bt,), float("inf"), **f), torch.zeros(Bt, **f)
+    status = torch.zeros(Bt, dtype=torch.int32, device=dev)
+    conv = torch.full((Bt,), -1, dtype=torch.int32, device=dev)
+    nrec = ops.unicycle_clf_cbf_records(0, numSteps, record_every)
+    traj = torch.empty(nrec, Bt, 3, **f) if record_every > 0 else None
+    us = torch.empty(nrec, Bt, 2, **f) if record_every > 0 else None
+    chunk = numSteps if not steps_per_launch else int(steps_per_launch)
+    if chunk < 1 and numSteps > 0:
+        raise ValueError("steps_per_launch must be >= 1")
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter()
+    t = 0
+    while t < numSteps:
+        k = min(chunk, numSteps - t)
+        r0 = ops.unicycle_clf_cbf_records(0, t, record_every)
+        ops.unicycle_clf_cbf_rollout(x, goal_b, cost, status, k, dt=dt, min_h=min_h, converged_at=conv,
+                                     traj=traj[r0:] if traj is not None else None, u_rec=us[r0:] if us is not None else None,
+                                     record_every=record_every, t_offset=t, **kw)
+        t += k
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter() - t_loop
+    collided = ~(min_h >= 0)
+    fails = status > 0
+    dist = (x[:, :2] - goal_b[:, :2]).norm(dim=-1)
+    stats = reduce_rollout_stats(collided.sum(), min_h.min(), cost.sum() / max(numSteps, 1), fails.sum(), Bt)
+    return dict(stats=stats, x_final=x, min_h=min_h, cost=cost, status=status, converged_at=conv, dist_to_goal=dist, traj=traj,
+                u=us, loop_seconds=t_loop)

@@ -223,6 +223,62 @@ class CLFCartesian:
     def __init__(self, Kp=(0.9, 1.5, 4.0)):
         self.Kp = torch.as_tensor(Kp, dtype=torch.float64)
 
+    def isconverged(self, x, state_goal):
+        """:613-615: rho < 1e-3."""
+        return cartesian2polar(x, state_goal)[..., 0] < 1e-3
+
+
+def _normalize_radians(theta):
+    return (theta + math.pi) % (2 * math.pi) - math.pi
+
+
+def cartesian2polar(state, state_goal):
+    """:112-139, batched over leading dimensions: (x, y, theta) relative to the goal -> (rho, alpha, beta), rho the distance to
+    the goal's position, alpha / beta the robot's / the goal's heading relative to the bearing of the goal.  The reference asserts
+    rho > 1e-6 for its one state; here a smaller rho is the caller's to refuse (the library's polar program does: status 1)."""
+    state, state_goal = torch.as_tensor(state), torch.as_tensor(state_goal).to(state)
+    xd, yd = state_goal[..., 0] - state[..., 0], state_goal[..., 1] - state[..., 1]
+    phi = torch.atan2(yd, xd)
+    return torch.stack([torch.sqrt(xd ** 2 + yd ** 2), _normalize_radians(state[..., 2] - phi),
+                        _normalize_radians(state_goal[..., 2] - phi)], dim=-1)
+
+
+def polar2cartesian(x, state_goal):
+    """:82-109, batched: the inverse of `cartesian2polar`."""
+    x, state_goal = torch.as_tensor(x), torch.as_tensor(state_goal).to(x)
+    rho, alpha, beta = x[..., 0], x[..., 1], x[..., 2]
+    phi = _normalize_radians(state_goal[..., 2] - beta)
+    return torch.stack([state_goal[..., 0] - rho * torch.cos(phi), state_goal[..., 1] - rho * torch.sin(phi),
+                        _normalize_radians(phi + alpha)], dim=-1)
+
+
+class CLFPolar:
+    """The reference's CLFPolar (:442-497; Aicardi et al. 1995): V = Kp0 rho^2 / 2 + Kp1 (1 - cos alpha) + Kp2 (1 - cos beta)
+    + Kp3 (1 - cos(beta - alpha)) on polar coordinates; batched torch, any device.  Inside the library it is clf_kind 1 of
+    bcbf_unicycle_clf_cbf_control / _rollout."""
+
+    def __init__(self, Kp=(0.6, 1.5, 4.0, 0.0)):
+        self.Kp = torch.as_tensor(Kp, dtype=torch.float64)
+
+    def clf_terms(self, polar, state_goal):
+        K = self.Kp.to(polar)
+        rho, alpha, beta = polar[..., 0], polar[..., 1], polar[..., 2]
+        return torch.stack([0.5 * K[0] * rho ** 2, K[1] * (1 - torch.cos(alpha)), K[2] * (1 - torch.cos(beta)),
+                            K[3] * (1 - torch.cos(beta - alpha))], dim=-1)
+
+    def grad_clf(self, polar, state_goal):
+        K = self.Kp.to(polar)
+        rho, alpha, beta = polar[..., 0], polar[..., 1], polar[..., 2]
+        sba = torch.sin(beta - alpha)
+        return torch.stack([K[0] * rho, K[1] * torch.sin(alpha) - K[3] * sba, K[2] * torch.sin(beta) + K[3] * sba], dim=-1)
+
+    def grad_clf_wrt_goal(self, polar, state_goal):
+        return torch.zeros_like(state_goal)
+
+    def isconverged(self, x, state_goal):
+        """:495-497: rho < 1e-3."""
+        return cartesian2polar(x, state_goal)[..., 0] < 1e-3
+
 
 class ObstacleCBF:
     """Parameters of the reference's ObstacleCBF (:618-696)."""
@@ -511,13 +567,68 @@ class ControllerCLF(ControllerCLFBayesian):
 
     def __init__(self, planner, u_dim=2, coordinate_converter=None, dynamics=None, clf=None, clf_gamma=10.0,
                  clf_relax_weight=10.0, cbfs=(), cbf_gammas=(), visualizer=None, device="cuda", dtype=torch.float64,
-                 **kw):
+                 solver="ipm", **kw):
         super().__init__(planner, u_dim=u_dim, dynamics=None, clf=clf, clf_gamma=10.0, cbfs=cbfs,
                          cbf_gammas=cbf_gammas, mean_dynamics=dynamics if isinstance(dynamics, AckermannDrive) else None,
                          device=device, dtype=dtype, **kw)
         self.clf_relax_weight = 10.0
+        # solver "ipm": the generic interior-point kernel, Cartesian rows only.  "exact": the program's closed form inside
+        # bcbf_unicycle_clf_cbf_control (fp32 or fp64) -- the only path that knows the polar coordinates
+        if solver not in ("ipm", "exact"):
+            raise ValueError("solver must be 'ipm' or 'exact', got %r" % (solver,))
+        polar_clf, polar_conv = isinstance(clf, CLFPolar), coordinate_converter is cartesian2polar
+        if polar_clf != polar_conv or (polar_clf and dynamics is not None and not isinstance(dynamics, PolarDynamics)):
+            raise ValueError("CLFPolar, cartesian2polar and PolarDynamics come together")
+        if polar_clf and solver != "exact":
+            raise ValueError("the polar controller needs solver='exact' (the 'ipm' path forms Cartesian rows only)")
+        if polar_clf and len(self.cbfs):
+            raise ValueError("the polar controller takes no obstacles: ObstacleCBF is stated in Cartesian coordinates")
+        self.solver, self.coordinate_converter, self.polar = solver, coordinate_converter, polar_clf
+
+    def isconverged(self, state, state_goal):
+        """:790-791."""
+        return self.clf.isconverged(state, state_goal)
+
+    def exact_task(self, Bt):
+        """Keywords of ops.unicycle_clf_cbf_control / _rollout for this controller (everything but the plan)."""
+        f = dict(dtype=self.dtype, device=self.device)
+        kw = dict(Kp=self.clf.Kp, clf_kind="polar" if self.polar else "cartesian", clf_gamma=float(self.clf_gamma),
+                  relax_weight=float(self.clf_relax_weight), lo=self.ctrl_min, hi=self.ctrl_max,
+                  L_ctrl=float(self.mean_dynamics.L))
+        if len(self.cbfs):
+            def per_instance(v, width):
+                v = v.to(**f).reshape(-1, width)
+                if v.shape[0] not in (1, Bt):
+                    raise ValueError("%d obstacle values for a batch of %d control loops" % (v.shape[0], Bt))
+                return v.expand(Bt, width)
+            kw.update(centers=torch.stack([per_instance(c.center, 2) for c in self.cbfs], dim=1).contiguous(),
+                      radii=torch.stack([per_instance(c.radius, 1)[:, 0] for c in self.cbfs], dim=1).contiguous(),
+                      tw=self.cbfs[0].term_weights, gammas=list(self.cbf_gammas))
+        return kw
+
+    def _control_exact(self, x_torch, t):
+        single = x_torch.dim() == 1
+        f = dict(dtype=self.dtype, device=self.device)
+        x = x_torch.reshape(-1, 3).to(**f).contiguous()
+        Bt = x.shape[0]
+        plan, dplan = self.planner.plan(t).to(**f), self.planner.dot_plan(t).to(**f)
+        plan = plan.expand(Bt, 3).contiguous() if plan.dim() == 1 else plan.contiguous()
+        dplan = dplan.expand(Bt, 3).contiguous() if dplan.dim() == 1 else dplan.contiguous()
+        out = ops.unicycle_clf_cbf_control(x, plan, dplan, want=("u", "status"), **self.exact_task(Bt))
+        self.last_status = out["status"]
+        u = out["u"]
+        if single:
+            if int(out["status"][0]) != 0:
+                raise ValueError("infeasible")
+            return u[0].to(device=x_torch.device, dtype=x_torch.dtype)
+        bad = out["status"] != 0
+        if bool(bad.any()):
+            u = torch.where(bad[:, None], torch.zeros_like(u), u)
+        return u.to(dtype=x_torch.dtype)
 
     def control(self, x_torch, t):
+        if self.solver == "exact":
+            return self._control_exact(x_torch, t)
         single = x_torch.dim() == 1
         f64 = dict(dtype=torch.float64, device=self.device)
         x = x_torch.reshape(-1, 3).to(**f64).contiguous()
@@ -755,3 +866,115 @@ unicycle_mean_cbf_collides_obstacle = _with_playback(unicycle_mean_cbf_collides_
 unicycle_bayes_cbf_safe_obstacle = _with_playback(unicycle_bayes_cbf_safe_obstacle_exp)
 unicycle_learning_helps_avoid_getting_stuck = _with_playback(unicycle_learning_helps_avoid_getting_stuck_exp)
 unicycle_no_learning_gets_stuck = _with_playback(unicycle_no_learning_gets_stuck_exp)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The model-based demos of the reference (:1456-1488, 1579-1656) on the one-launch rollout of the mean-model controller
+# (bcbf_unicycle_clf_cbf_rollout): the planner, the rows, the program and the plant step of every step run inside the kernel.
+def _plant_L(dynamics):
+    if dynamics is None or isinstance(dynamics, CartesianDynamics):
+        return 1.0
+    if isinstance(dynamics, AckermannDrive):
+        return float(dynamics.L)
+    raise ValueError("the plant of the in-kernel loop is CartesianDynamics or AckermannDrive, got %r" % (dynamics,))
+
+
+def clf_rollout(controller, x0, numSteps, dt, dynamics=None, stop_rho=0.0):
+    """numSteps steps of `controller` (a ControllerCLF with solver='exact' on a NoPlanner or a PiecewiseLinearPlanner) from
+    x0[3] or x0[Bt,3] on the plant `dynamics` in one launch, every step recorded.
+    Returns dict(X[numSteps+1,...,3], U[numSteps,...,2], Xdot[numSteps,...,3], status, converged_at, min_h, cost)."""
+    if not isinstance(controller, ControllerCLF) or controller.solver != "exact":
+        raise ValueError("the in-kernel loop runs a ControllerCLF(solver='exact')")
+    f = dict(dtype=controller.dtype, device=controller.device)
+    x0 = torch.as_tensor(x0)
+    lead = tuple(x0.shape[:-1])
+    x = x0.reshape(-1, 3).to(**f).contiguous().clone()
+    Bt = x.shape[0]
+    planner = controller.planner
+    if isinstance(planner, NoPlanner):
+        pk = dict(planner="none")
+        goal = planner.x_goal
+    elif isinstance(planner, PiecewiseLinearPlanner):
+        pk = dict(planner="piecewise", x0_plan=torch.as_tensor(planner.x0).to(**f).reshape(-1, 3).expand(Bt, 3).contiguous(),
+                  numStepsPlan=planner.numSteps, frac_time_to_reach_goal=planner.frac_time_to_reach_goal)
+        if float(planner.dt) != float(dt):
+            raise ValueError("the in-kernel planner runs on the loop's dt (%r), the planner was built with %r" % (dt, planner.dt))
+        goal = planner.x_goal
+    else:
+        raise ValueError("the in-kernel loop knows NoPlanner and PiecewiseLinearPlanner, got %r" % (planner,))
+    goal = torch.as_tensor(goal).to(**f).reshape(-1, 3).expand(Bt, 3).contiguous()
+    i32 = dict(dtype=torch.int32, device=controller.device)
+    min_h, cost = torch.full((Bt,), float("inf"), **f), torch.zeros(Bt, **f)
+    status, conv = torch.zeros(Bt, **i32), torch.full((Bt,), -1, **i32)
+    X, U = torch.empty(numSteps + 1, Bt, 3, **f), torch.zeros(numSteps, Bt, 2, **f)
+    ops.unicycle_clf_cbf_rollout(x, goal, cost, status, numSteps, dt=float(dt), min_h=min_h, converged_at=conv,
+                                 L_true=_plant_L(dynamics), stop_rho=float(stop_rho), traj=X, u_rec=U, record_every=1, **pk,
+                                 **controller.exact_task(Bt))
+    X[numSteps] = x
+    L = _plant_L(dynamics)
+    th = X[:-1, :, 2]
+    Xdot = torch.stack([th.cos() * U[..., 0], th.sin() * U[..., 0], U[..., 1] / L], dim=-1)
+    shape = lambda T, w: T.reshape((T.shape[0],) + lead + (w,))
+    return dict(X=shape(X, 3), U=shape(U, 2), Xdot=shape(Xdot, 3), status=status.reshape(lead), converged_at=conv.reshape(lead),
+                min_h=min_h.reshape(lead), cost=cost.reshape(lead))
+
+
+def move_to_pose(state_start, state_goal, dt=0.01, show_animation=False, controller=None, dynamics=None, visualizer=None,
+                 max_steps=10000):
+    """:1456-1488: step `controller` on `dynamics` until controller.isconverged (rho < 1e-3).  The reference's loop is unbounded
+    and returns nothing; this one stops after max_steps and returns what the reference's visualiser is shown:
+    (X[T+1,3], U[T,2]) for one start, T the step at which it converged (max_steps if it did not); for a batch of starts
+    [Bt,3], (X[T+1,Bt,3], U[T,Bt,2], converged_at[Bt]) with T the last instance's (a converged instance stays where it is,
+    u = 0; -1 in converged_at: not converged within max_steps)."""
+    out = clf_rollout(controller, state_start, max_steps, dt, dynamics=dynamics, stop_rho=1e-3)
+    conv = out["converged_at"]
+    if int((out["status"] != 0).sum()):
+        raise ValueError("infeasible")
+    T = max_steps if bool((conv < 0).any()) else int(conv.max())
+    if conv.dim() == 0:
+        return out["X"][:T + 1], out["U"][:T]
+    return out["X"][:T + 1], out["U"][:T], conv
+
+
+def _clf_controller(x_g, clf_kind, device, dtype, planner=None, **kw):
+    x_g = torch.as_tensor(x_g, dtype=dtype, device=device)
+    planner = planner or NoPlanner(x_g)
+    if clf_kind == "polar":
+        return ControllerCLF(planner, coordinate_converter=cartesian2polar, dynamics=PolarDynamics(), clf=CLFPolar(),
+                             solver="exact", device=device, dtype=dtype, **kw)
+    return ControllerCLF(planner, coordinate_converter=lambda x, xg: x, dynamics=CartesianDynamics(),
+                         clf=kw.pop("clf", None) or CLFCartesian(), solver="exact", device=device, dtype=dtype, **kw)
+
+
+def move_to_pose_clf_polar(x, x_g, dt=None, device="cuda", dtype=torch.float64, **kw):
+    """:1579-1591 (Aicardi et al.'s polar controller on the Cartesian unicycle)."""
+    return move_to_pose(x, x_g, dynamics=CartesianDynamics(), controller=_clf_controller(x_g, "polar", device, dtype), dt=dt, **kw)
+
+
+def move_to_pose_clf_cartesian(x, x_g, dt=None, device="cuda", dtype=torch.float64, **kw):
+    """:1593-1605."""
+    return move_to_pose(x, x_g, dynamics=CartesianDynamics(), controller=_clf_controller(x_g, "cartesian", device, dtype), dt=dt,
+                        **kw)
+
+
+def move_to_pose_sample_clf_cartesian(x, x_g, dt=None, device="cuda", dtype=torch.float64, D=200):
+    """:1616-1628: sample_generator_trajectory's (Xdot[D,3], X[D+1,3], U[D,2]) of 200 steps under the Cartesian CLF."""
+    out = clf_rollout(_clf_controller(x_g, "cartesian", device, dtype), x, D, dt, dynamics=CartesianDynamics())
+    if int((out["status"] != 0).sum()):
+        raise ValueError("infeasible")
+    return out["Xdot"], out["X"], out["U"]
+
+
+def track_trajectory_clf_cartesian(x, x_g, dt=None, cbfs=None, cbf_gammas=None, numSteps=None, Kp=(0.9, 1.5, 0.0),
+                                   device="cuda", dtype=torch.float64):
+    """:1630-1656: (Xdot[numSteps,3], X[numSteps+1,3], U[numSteps,2]) of the Cartesian CLF-CBF controller tracking
+    PiecewiseLinearPlanner(x, x_g, numSteps, dt) past the obstacles cbfs(x, x_g)."""
+    f = dict(dtype=dtype, device=device)
+    x, x_g = torch.as_tensor(x, **f), torch.as_tensor(x_g, **f)
+    planner = PiecewiseLinearPlanner(x, x_g, numSteps, dt)
+    ctrl = _clf_controller(x_g, "cartesian", device, dtype, planner=planner, clf=CLFCartesian(Kp=Kp),
+                           cbfs=cbfs(x, x_g) if cbfs is not None else (), cbf_gammas=list(cbf_gammas or ()))
+    out = clf_rollout(ctrl, x, numSteps, dt, dynamics=CartesianDynamics())
+    if int((out["status"] != 0).sum()):
+        raise ValueError("infeasible")
+    return out["Xdot"], out["X"], out["U"]

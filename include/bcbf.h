@@ -1298,6 +1298,102 @@ int bcbf_pendulum_clf_cbf_rollout_f64(double* x, const double* ctrl_params, int 
                                       double cbf_gamma, int cbf_kind, double slack_weight, double dt, double* min_h,
                                       int* damage, int* status, double* traj, double* u_rec, int record_every, int t_offset,
                                       int numSteps, int Bt, void* stream);
+
+/* ---- The unicycle's CLF-CBF quadratic program on the MEAN model (ControllerCLF, unicycle_move_to_pose.py:699-791; the
+ * controller of move_to_pose_clf_polar / _clf_cartesian / _sample_clf_cartesian / track_trajectory_clf_cartesian, :1579-1656,
+ * and of the speed test's trajectories, :2072-2083).  y = (u0, u1, relax):
+ *     minimise |u|^2 + relax_weight relax   subject to   lo <= u <= hi,   a_0.u + b_0 - relax <= 0,   a_k.u + b_k >= 0 (k >= 1).
+ * relax is free with a positive linear cost, so its row is tight and u* is the Euclidean projection of p = -(relax_weight/2) a_0
+ * onto the polygon {box} n {hard rows}; relax* = a_0.u* + b_0 (it may be negative).  The optimum is unique; the program is
+ * infeasible exactly when the polygon is empty.  The projection is found by enumerating active sets of size <= 2 over the
+ * M = 4 + Kob half-planes in the order lo0, lo1, hi0, hi1, hard rows (Kob <= 3, at most 29 candidates): p; the foot of p on each
+ * line in row order (zero normal: no candidate); each pairwise intersection in lexicographic order (determinant exactly 0: no
+ * candidate).  A candidate is admissible when every row i NOT in its active set has a_i.u + b_i >= -tol_i,
+ * tol_i = 64 eps (|a_i0 u0| + |a_i1 u1| + |b_i|); the answer is the admissible candidate nearest to p, ties to the first in
+ * that order.  No admissible candidate, or a non-finite row or result: status 1 and u, relax, active are NOT written.  The
+ * reference iterates with GUROBI through cvxpy; parity with its iterates is not claimed.
+ *
+ * The program alone: a[Bt,K,2], b[Bt,K] (row 0 relaxed, rows 1.. hard, 1 <= K <= 4); lo[2], hi[2], relax_weight: HOST values.
+ * -> u[Bt,2], relax[Bt], active[Bt] (int bitmask over the M rows: the winning candidate's active set), status[Bt] (int);
+ * every output may be NULL.
+ * BCBF_EINVAL with a reason in bcbf_last_error, before any HIP call, for: Bt <= 0, K outside 1..4, null a / b / lo / hi, a
+ * non-finite bound, relax_weight not a finite number > 0. */
+int bcbf_clf_cbf_qp2_f32(const float* a, const float* b, const float* lo, const float* hi, float relax_weight, float* u,
+                         float* relax, int* active, int* status, int Bt, int K, void* stream);
+int bcbf_clf_cbf_qp2_f64(const double* a, const double* b, const double* lo, const double* hi, double relax_weight, double* u,
+                         double* relax, int* active, int* status, int Bt, int K, void* stream);
+
+/* One control evaluation (ControllerCLF.control, :757-788; _clc :731-742, _cbcs :744-752) for Bt states x[Bt,3] with
+ * plan[Bt,3], dot_plan[Bt,3].  Kp[4], lo[2], hi[2], tw[2], gammas[Kob]: HOST values.
+ *   clf_kind 0: CLFCartesian (:522-615, Kp[0..2]) and ObstacleCBF (:618-696) on AckermannDrive(L_ctrl) / CartesianDynamics
+ *     (L_ctrl = 1), f = 0: a_k = grad_k . g(x; L_ctrl), b_0 = grad_goal V . dot_plan + clf_gamma V, b_k = gammas[k-1] h_k -- the
+ *     rows of bcbf_unicycle_constraints;
+ *   clf_kind 1: CLFPolar (:442-497) on PolarDynamics (:143-167) through cartesian2polar (:112-139), (rho, alpha, beta) of x
+ *     relative to plan:  V = Kp0 rho^2 / 2 + Kp1 (1 - cos alpha) + Kp2 (1 - cos beta) + Kp3 (1 - cos(beta - alpha)),
+ *     a_0 = grad V . [[-cos alpha, 0], [-sin alpha / rho, 1], [-sin alpha / rho, 0]],  b_0 = clf_gamma V (grad_clf_wrt_goal = 0);
+ *     rho <= 1e-6 is refused as the reference's assert does (status 1).  Kob must be 0: the reference would hand polar
+ *     coordinates to ObstacleCBF.
+ * L_ctrl: device, one shared value (L_stride 0) or one per instance (1).  centers[.,Kob,2], radii[.,Kob]: device, shared
+ * (obs_stride 0) or per instance (1); unused with Kob = 0.
+ * -> a[Bt,1+Kob,2], b[Bt,1+Kob], values[Bt,1+Kob] = (V, h_k), u[Bt,2], relax[Bt], active[Bt], status[Bt]; each may be NULL;
+ * u, relax and active are not written where status is 1.
+ * BCBF_EINVAL with a reason, before any HIP call, for every refusal of the program's entry and: null x / plan / dot_plan / Kp /
+ * L_ctrl, Kob outside 0..3, clf_kind not 0 / 1, clf_kind 1 with Kob > 0, a stride not 0 / 1, a non-finite clf_gamma,
+ * Kob > 0 with null centers / radii / tw / gammas. */
+int bcbf_unicycle_clf_cbf_control_f32(const float* x, const float* plan, const float* dot_plan, const float* Kp, int clf_kind,
+                                      float clf_gamma, float relax_weight, const float* lo, const float* hi,
+                                      const float* L_ctrl, int L_stride, const float* centers, const float* radii,
+                                      int obs_stride, const float* tw, const float* gammas, float* a, float* b, float* values,
+                                      float* u, float* relax, int* active, int* status, int Bt, int Kob, void* stream);
+int bcbf_unicycle_clf_cbf_control_f64(const double* x, const double* plan, const double* dot_plan, const double* Kp,
+                                      int clf_kind, double clf_gamma, double relax_weight, const double* lo, const double* hi,
+                                      const double* L_ctrl, int L_stride, const double* centers, const double* radii,
+                                      int obs_stride, const double* tw, const double* gammas, double* a, double* b,
+                                      double* values, double* u, double* relax, int* active, int* status, int Bt, int Kob,
+                                      void* stream);
+
+/* The closed loop (sample_generator_trajectory over ControllerCLF.control, sampling.py:40-80; move_to_pose's while loop,
+ * :1456-1488): numSteps steps for Bt instances in ONE launch, one lane per instance (64-thread workgroups); state, parameters,
+ * the planner's control points and the statistics stay in registers.  Per (0-based) step t, global step T = t_offset + t:
+ *   0. stop_rho > 0: where |goal - x_t| (positions) < stop_rho (isconverged, :495-497, 613-615) the instance records
+ *      converged_at = T and stops: state frozen, status stays 0.  converged_at[Bt] (int, in/out): -1 = still running.
+ *   1. the plan.  planner_kind 0 (NoPlanner): plan = goal[b], dot_plan = 0.  planner_kind 1 (PiecewiseLinearPlanner,
+ *      planner.py:19-64, with the SAME dt): control points from x0_plan[Bt,3] and goal[Bt,3], evaluated at
+ *      min(T + lookahead, numStepsPlan); the integers t2 = min(int(numStepsPlan frac), numStepsPlan - 1),
+ *      lookahead = max(int(0.1 numStepsPlan), 1) and numStepsPlan are the HOST's (no float-to-int rule on the device);
+ *   2. the rows at x_t on the controller's model (L_ctrl), as the control entry forms them;
+ *   3. the program;
+ *   4. min_h = min(min_h, min_k h_k(x_t)) (non-finite counts as -inf; untouched, and may be NULL, with Kob = 0);
+ *      cost += |u_t|^2;
+ *   5. x_{t+1} = x_t + g(x_t; L_true) u_t dt on the PLANT's wheelbase (L_true: as L_ctrl; a plant that differs from the
+ *      controller's model is the mismatch study).  No angle wrap: the reference applies none.
+ * An instance whose program cannot be solved at step t records status = T + 1 and freezes: state and statistics keep the
+ * values they had before that step.  An instance that arrives with status != 0 or converged_at >= 0 stays as it is.
+ * In/out, accumulated in place: x[Bt,3], min_h[Bt], cost[Bt], status[Bt] (int), converged_at[Bt] (int; may be NULL when
+ * stop_rho = 0) -- two calls of k and n - k steps, the second with t_offset = k, equal one call of n steps bit for bit.
+ * Recording (traj and/or u_rec given, record_every > 0): the steps whose T is a multiple of record_every write (x_t, u_t) --
+ * before the step; u = 0 for a frozen or stopped instance -- to traj[r,Bt,3] and u_rec[r,Bt,2], r counting from 0 within
+ * THIS launch.
+ * BCBF_EINVAL with a reason, before any HIP call, for every refusal of the control entry's task arguments and: Bt <= 0,
+ * numSteps < 0, t_offset < 0 or t_offset + numSteps overflowing, dt not a finite number > 0, stop_rho negative or not finite,
+ * stop_rho > 0 without converged_at, null x / goal / cost / status / L_true, null min_h with Kob > 0, planner_kind not 0 / 1,
+ * planner_kind 1 without x0_plan or with numStepsPlan < 3, t2 outside [0, numStepsPlan), lookahead outside [1, numStepsPlan],
+ * recording pointers with record_every <= 0. */
+int bcbf_unicycle_clf_cbf_rollout_f32(float* x, const float* goal, const float* x0_plan, int planner_kind, int t2,
+                                      int lookahead, int numStepsPlan, const float* Kp, int clf_kind, float clf_gamma,
+                                      float relax_weight, const float* lo, const float* hi, const float* L_ctrl, int Lc_stride,
+                                      const float* L_true, int Lt_stride, const float* centers, const float* radii,
+                                      int obs_stride, const float* tw, const float* gammas, float dt, float stop_rho,
+                                      float* min_h, float* cost, int* status, int* converged_at, float* traj, float* u_rec,
+                                      int record_every, int t_offset, int numSteps, int Bt, int Kob, void* stream);
+int bcbf_unicycle_clf_cbf_rollout_f64(double* x, const double* goal, const double* x0_plan, int planner_kind, int t2,
+                                      int lookahead, int numStepsPlan, const double* Kp, int clf_kind, double clf_gamma,
+                                      double relax_weight, const double* lo, const double* hi, const double* L_ctrl,
+                                      int Lc_stride, const double* L_true, int Lt_stride, const double* centers,
+                                      const double* radii, int obs_stride, const double* tw, const double* gammas, double dt,
+                                      double stop_rho, double* min_h, double* cost, int* status, int* converged_at,
+                                      double* traj, double* u_rec, int record_every, int t_offset, int numSteps, int Bt,
+                                      int Kob, void* stream);
 /* The same control step on a model learned with the opt-in Matern-5/2 data kernel (bcbf_refit_matern52 /
  * bcbf_gp_append_matern52 states): identical arguments; the posterior launch evaluates the Matern kernel (one GP per
  * instance: the streaming kernel; shared_gp: the matrix-core query bcbf_posterior_shared_matern52), the fused task rows /
