@@ -142,6 +142,10 @@ _TSIGS = {
                                       P, P, c_int, "PT", "PT", "T", "T"] + [P] * 6 + [c_int] * 5 + [P],
     # LQRController.control (controllers.py:64-115) and the two bdlqr LinearSystem solves inside it; x_goal, Q, R: HOST values
     "bcbf_lqr_nominal": [P, P, P, "PT", "PT", "PT", "T", c_int, c_int, P, P, P, P, c_int, c_int, c_int, P],
+    # the obstacle-field working set: select, audit (gamma: "T"; tol_f, tol_a: doubles for both precisions), commit
+    "bcbf_obstacle_field_select": [P, P, P, c_int, P] + [P] * 6 + [c_int] * 3 + [P],
+    "bcbf_obstacle_field_audit": [P] * 11 + [c_int, P, "T", c_double, c_double] + [P] * 8 + [c_int] * 3 + [P],
+    "bcbf_obstacle_field_commit": [P] * 5 + ["T", "T", c_int, P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],
     "bcbf_unicycle_control_step": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
     "bcbf_unicycle_control_step_matern52": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],

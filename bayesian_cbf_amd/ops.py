@@ -1417,6 +1417,134 @@ def control_workspace(Bt, Kob, dtype, device, n=3, m=2):
                 y=torch.empty(Bt, m + 1, **f), status=torch.empty(Bt, **i), iters=torch.empty(Bt, **i))
 
 
+# ------------------------------------------------------------------------------------------------ obstacle fields
+# (bcbf.h "Obstacle fields": a working set of S <= 3 discs in the fused solver, certified against a field of up to MAX_FIELD)
+MAX_FIELD = 256
+FIELD_CERTIFIED, FIELD_FULL, FIELD_UNSOLVED, FIELD_UNCERTIFIED = 1, 2, 3, 6
+# (tol_f, tol_a) of the audit: fp64 = the solvers' acceptance and ten times it; fp32 measured, bcbf.h BCBF_FIELD_TOL_*_F32
+FIELD_TOLERANCES = {torch.float64: (1e-7, 1e-6), torch.float32: (5e-7, 7e-6)}
+
+
+def _field_args(x, field):
+    """(centers_f[Bf,Kf,2], radii_f[Bf,Kf], field_stride, Kf) of field = dict(centers, radii): a leading axis of 1 (or none) is one
+    field shared by every instance, a leading axis of Bt one field per instance."""
+    cen, rad = field["centers"], field["radii"]
+    if cen.dim() == 2:
+        cen, rad = cen[None], rad[None]
+    _chk(x, cen, rad)
+    Bt, Kf = x.shape[0], rad.shape[1]
+    if cen.shape != (rad.shape[0], Kf, 2) or rad.shape[0] not in (1, Bt):
+        raise ValueError("field: centers[Bf,Kf,2] and radii[Bf,Kf] with Bf = 1 (shared) or Bt")
+    if not 1 <= Kf <= MAX_FIELD:
+        raise ValueError("a field holds 1..%d discs, got %d" % (MAX_FIELD, Kf))
+    return cen, rad, (1 if rad.shape[0] == Bt and Bt > 1 else 0), Kf
+
+
+def obstacle_field_workspace(Bt, S, dtype, device):
+    """Buffers of the obstacle-field step: the working set (idx[Bt,S], centers_sel[Bt,S,2], radii_sel[Bt,S] -- the control step's
+    task['centers'] / task['radii']), the certificate (cert, rounds, worst_margin, worst_idx, nviol, status_eff) and the loop's
+    statistics (min_h = +inf, cost = 0, fails = 0)."""
+    f = dict(dtype=dtype, device=device)
+    i = dict(dtype=torch.int32, device=device)
+    return dict(idx=torch.zeros(Bt, S, **i), centers_sel=torch.zeros(Bt, S, 2, **f), radii_sel=torch.ones(Bt, S, **f),
+                cert=torch.zeros(Bt, **i), rounds=torch.zeros(Bt, **i), worst_margin=torch.zeros(Bt, **f),
+                worst_idx=torch.zeros(Bt, **i), nviol=torch.zeros(Bt, **i), status_eff=torch.zeros(Bt, **i),
+                min_h=torch.full((Bt,), float("inf"), **f), cost=torch.zeros(Bt, **f), fails=torch.zeros(Bt, **i))
+
+
+def obstacle_field_select(x, field, tw, fws):
+    """bcbf_obstacle_field_select: the S = fws['idx'].shape[1] discs of smallest h_k(x) into the working set; min_h over the whole
+    field; cert = rounds = 0."""
+    cen, rad, stride, Kf = _field_args(x, field)
+    _chk(x, tw, fws["idx"], fws["centers_sel"], fws["radii_sel"], fws["min_h"], fws["cert"], fws["rounds"])
+    Bt, S = fws["idx"].shape
+    check(getattr(lib, "bcbf_obstacle_field_select" + _suf(x))(
+        _p(x), _p(cen), _p(rad), stride, _p(tw), _p(fws["idx"]), _p(fws["centers_sel"]), _p(fws["radii_sel"]), _p(fws["min_h"]),
+        _p(fws["cert"]), _p(fws["rounds"]), Bt, Kf, S, _stream(x)), "bcbf_obstacle_field_select")
+    return fws["idx"]
+
+
+def obstacle_field_audit(x, ws, A, rho, field, tw, gamma, fws, tol_f=None, tol_a=None):
+    """bcbf_obstacle_field_audit at the control ws['y'] of the working-set solve (run with dt = 0, so x is the state the program
+    was formed at): certify, declare the working set full, or swap the worst violator in for the slack-most slot (bcbf.h)."""
+    cen, rad, stride, Kf = _field_args(x, field)
+    _chk(x, ws["y"], ws["status"], ws["Mk"], ws["Bk"], A, ws["fhat"], ws["ghat"], rho, tw, fws["idx"], fws["centers_sel"],
+         fws["radii_sel"], fws["cert"], fws["rounds"], fws["worst_margin"], fws["worst_idx"], fws["nviol"])
+    Bt, S = fws["idx"].shape
+    if A.shape[0] != Bt:
+        raise ValueError("A must be [Bt,3,3] (one kernel matrix per instance, as the fused step reads it)")
+    d_f, d_a = FIELD_TOLERANCES[x.dtype]
+    check(getattr(lib, "bcbf_obstacle_field_audit" + _suf(x))(
+        _p(x), _p(ws["y"]), _p(ws["status"]), _p(ws["Mk"]), _p(ws["Bk"]), _p(A), _p(ws["fhat"]), _p(ws["ghat"]), _p(rho),
+        _p(cen), _p(rad), stride, _p(tw), float(gamma), d_f if tol_f is None else float(tol_f),
+        d_a if tol_a is None else float(tol_a), _p(fws["idx"]), _p(fws["centers_sel"]), _p(fws["radii_sel"]), _p(fws["cert"]),
+        _p(fws["rounds"]), _p(fws["worst_margin"]), _p(fws["worst_idx"]), _p(fws["nviol"]), Bt, Kf, S, _stream(x)),
+        "bcbf_obstacle_field_audit")
+    return fws["cert"]
+
+
+def obstacle_field_commit(x, y, status, fws, dt=0.0, L_true=1.0):
+    """bcbf_obstacle_field_commit: status_eff (0 = certified optimum of the full program), and the plant step of exactly those."""
+    _chk(x, y, status, fws["cert"], fws["status_eff"])
+    check(getattr(lib, "bcbf_obstacle_field_commit" + _suf(x))(
+        _p(x), _p(y), _p(status), _p(fws["cert"]), _p(fws["status_eff"]), dt, L_true, x.shape[0], _stream(x)),
+        "bcbf_obstacle_field_commit")
+    return fws["status_eff"]
+
+
+def unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=3, dt=0.0, L_true=1.0, L_mean=1.0, clf_gamma=10.0,
+                                        max_iters=100, fws=None, tol_f=None, tol_a=None, stats=True):
+    """The chance-constrained control step among the Kf <= 256 discs of `field` = dict(centers[Bf,Kf,2], radii[Bf,Kf]) (Bf = 1: one
+    field for all instances).  Returns step(): on the current stream, with no host look at the device (capturable),
+        select -> the fused control step on the working set (dt = 0) -> audit
+        -> (rounds - 1) x [the same step in its Lop = NULL form on ws['Mk'], ws['Bk'] -> audit] -> commit -> rollout_stats.
+    An instance certified in an earlier round is solved again and reproduces its y (the solver is deterministic and
+    position-independent); the audit leaves it alone.  task: as `unicycle_control_step`, for S = task['sign'].shape[0] - 1 <= 3
+    obstacle slots -- sign[1+S], relax_mask[1+S], gammas[S] all equal (one gamma for the field; mixed gammas raise ValueError);
+    its 'centers' / 'radii' are replaced by the working set's.  ws = control_workspace(Bt, S); fws = obstacle_field_workspace(Bt, S)
+    (made here when None): step.fws.  status_eff[b] = 0 where the step is the certified optimum of the FULL program and the plant
+    moved (dt > 0); BCBF_FIELD_UNCERTIFIED (6) where `rounds` did not suffice or the working set is full; the solver's status
+    where the working-set program was not solved.  The observing, sampled and self-triggered steps are out of scope."""
+    if rounds < 1:
+        raise ValueError("rounds must be >= 1")
+    Bt = x.shape[0]
+    S = task["sign"].shape[0] - 1
+    if not 1 <= S <= 3:
+        raise ValueError("the working set holds 1..3 obstacle slots (task['sign'] has 1 + S rows), got %d" % S)
+    gam = task["gammas"]
+    if gam.shape[0] != S or not bool((gam == gam[0]).all()):
+        raise ValueError("an obstacle field has one gamma: task['gammas'] must hold S equal values")
+    gamma = float(gam[0])
+    cen, rad, stride, Kf = _field_args(x, field)
+    if Kf < S:
+        raise ValueError("the field holds fewer discs (%d) than the working set has slots (%d)" % (Kf, S))
+    if fws is None:
+        fws = obstacle_field_workspace(Bt, S, x.dtype, x.device)
+    task = dict(task, centers=fws["centers_sel"], radii=fws["radii_sel"])
+    field = dict(centers=cen, radii=rad)
+    first = unicycle_control_step_prepare(gp, task, ws, x, 0.0, L_true, L_mean, clf_gamma, max_iters)
+    again = first
+    if rounds > 1 and gp.get("Lop") is not None:
+        again = unicycle_control_step_prepare(dict(A=gp["A"]), task, ws, x, 0.0, L_true, L_mean, clf_gamma, max_iters)
+    _, A, _, _ = _control_step_args(gp, task, ws, x)
+    tw, rho, w = task["tw"], task["rho"], task["w"]
+
+    def step():
+        obstacle_field_select(x, field, tw, fws)
+        first()
+        obstacle_field_audit(x, ws, A, rho, field, tw, gamma, fws, tol_f, tol_a)
+        for _ in range(rounds - 1):
+            again()
+            obstacle_field_audit(x, ws, A, rho, field, tw, gamma, fws, tol_f, tol_a)
+        obstacle_field_commit(x, ws["y"], ws["status"], fws, dt, L_true)
+        if stats:
+            rollout_stats(ws["cst"], ws["y"], fws["status_eff"], w, gam, fws["min_h"], fws["cost"], fws["fails"])
+        return ws["y"]
+    step.fws = fws
+    step.keep = (first, again, task, field, A)
+    return step
+
+
 def trigger_workspace(Bt, dtype, device):
     """Buffers of `unicycle_trigger_step_prepare`: every instance's clock t[Bt] (fp64 whatever the working type) and event count
     events[Bt] (int32), both zero, and the outputs of one event -- tau, dt_used, Lfh, Lkd[Bt,3], Lh, xvel, uBu (zero: a finished

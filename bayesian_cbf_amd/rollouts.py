@@ -162,6 +162,133 @@ def monte_carlo_safety_rollouts(Bt, numSteps=200, dt=0.05, gp=None, kernel_diag_
     return out
 
 
+def random_obstacle_field(Kf, start=(-3.0, -1.0, -math.pi / 4), goal=(0.0, 0.0, math.pi / 4), seed=0,
+                          box=((-3.5, 0.5), (-2.0, 1.0)), radius=(0.1, 0.35), clear_start=0.5, clear_goal=0.4,
+                          dtype=torch.float64, device="cpu"):
+    """Kf discs for `obstacle_field_rollouts`: centres uniform in `box`, radii uniform in `radius`; a disc is rejected when its
+    centre is closer than radius + clear_start to the start or radius + clear_goal to the goal.  Drawn on the host from
+    numpy's seeded RandomState (the same discs on every device).  Returns dict(centers[Kf,2], radii[Kf])."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    cen, rad = [], []
+    while len(rad) < Kf:
+        c = (rng.uniform(*box[0]), rng.uniform(*box[1]))
+        r = rng.uniform(*radius)
+        if math.hypot(c[0] - start[0], c[1] - start[1]) < r + clear_start or math.hypot(c[0] - goal[0], c[1] - goal[1]) < r + clear_goal:
+            continue
+        cen.append(c)
+        rad.append(r)
+    return dict(centers=torch.tensor(np.array(cen).reshape(Kf, 2), dtype=dtype, device=device),
+                radii=torch.tensor(np.array(rad), dtype=dtype, device=device))
+
+
+def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_diag_A=(1e-2, 1e-2, 1e-2), L_mean=1.0, L_true=12.0,
+                            start=(-3.0, -1.0, -math.pi / 4), goal=(0.0, 0.0, math.pi / 4), start_noise=0.05, max_risk=0.01,
+                            dtype=torch.float64, device="cuda", seed=0, slots=3, rounds=3, record=False, max_iters=30,
+                            use_graph=False, tol_f=None, tol_a=None):
+    """`monte_carlo_safety_rollouts` among the discs of `field` = dict(centers[Kf,2] or [Bt,Kf,2], radii) -- up to 256 of them
+    (`random_obstacle_field`): every step solves the program on a working set of `slots` discs and certifies it against the whole
+    field (`ops.unicycle_field_control_step_prepare`, at most `rounds` solves).  A step that is not certified, or not solved, is
+    not taken: that instance keeps its state for the step and counts as a failure, as an unsolved program does there.
+    The result of `monte_carlo_safety_rollouts` (min_h over the WHOLE field), plus over all instance-steps:
+    certified_steps, rounds_hist[rounds] (certified after r swaps), uncertified_steps (rounds ran out), full_set_steps (every slot
+    active and a disc still violated), unsolved_steps (the working-set program was not solved); with record, traj[numSteps+1,Bt,3],
+    y[numSteps,Bt,3], cert, rounds_rec, status_eff [numSteps,Bt] and idx[numSteps,Bt,slots]."""
+    dev = torch.device(device)
+    f = dict(dtype=dtype, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    x0 = torch.tensor(start, **f)
+    xg = torch.tensor(goal, **f)
+    S = int(slots)
+    task = unicycle_task_tensors(Bt, x0, xg, dtype, dev, max_risk=max_risk, cbf_gammas=(5.0,) * S)
+    task["sign"] = torch.tensor([-1.0] + [1.0] * S, **f)
+    task["relax_mask"] = torch.tensor([1.0] + [0.0] * S, **f)
+    field = dict(centers=field["centers"].to(**f).contiguous(), radii=field["radii"].to(**f).contiguous())
+    planner = PiecewiseLinearPlanner(x0, xg, numSteps, dt, frac_time_to_reach_goal=0.95)
+    x = (x0 + start_noise * torch.randn(Bt, 3, generator=gen, **f)).contiguous()
+    ws = ops.control_workspace(Bt, S, dtype, dev)
+    fws = ops.obstacle_field_workspace(Bt, S, dtype, dev)
+    if gp is None:
+        A = torch.diag(torch.tensor(kernel_diag_A, **f)).expand(Bt, 3, 3).contiguous()
+        ws["Mk"].zero_()
+        ws["Bk"].copy_(torch.eye(3, **f).expand(Bt, 3, 3))
+        gp = dict(A=A)
+    plan_all = torch.stack([planner.plan(t).to(dtype=dtype) for t in range(numSteps)]).to(dev)
+    dplan_all = torch.stack([planner.dot_plan(t).to(dtype=dtype) for t in range(numSteps)]).to(dev)
+    task["plan"], task["dot_plan"] = torch.empty(Bt, 3, **f), torch.empty(Bt, 3, **f)
+    # counters of the certificate, accumulated on the device: [certified after 0 .. rounds-1 swaps | uncertified | full | unsolved]
+    counts = torch.zeros(rounds + 3, dtype=torch.long, device=dev)
+    bin_ids = torch.arange(rounds + 3, **i32)
+    state =[x, fws["min_h"], fws["cost"], fws["fails"], counts]
+    step = ops.unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=rounds, dt=dt, L_true=L_true, L_mean=L_mean,
+                                                   max_iters=max_iters, fws=fws, tol_f=tol_f, tol_a=tol_a)
+    rec = None
+    if record:
+        rec = dict(traj=torch.empty(numSteps + 1, Bt, 3, **f), y=torch.empty(numSteps, Bt, 3, **f),
+                   cert=torch.empty(numSteps, Bt, **i32), rounds_rec=torch.empty(numSteps, Bt, **i32),
+                   status_eff=torch.empty(numSteps, Bt, **i32), idx=torch.empty(numSteps, Bt, S, **i32))
+        rec["traj"][0] = x
+
+    def one_step(t):
+        if torch.is_tensor(t):
+            task["plan"].copy_(plan_all.index_select(0, t))
+            task["dot_plan"].copy_(dplan_all.index_select(0, t))
+        else:
+            task["plan"].copy_(plan_all[t])
+            task["dot_plan"].copy_(dplan_all[t])
+        step()
+        cert, eff = fws["cert"], fws["status_eff"]
+        # bin per instance: certified -> its number of swaps; else rounds (uncertified), rounds + 1 (full), rounds + 2 (unsolved)
+        other = rounds + 2 - 2 * (eff == ops.FIELD_UNCERTIFIED).to(torch.int32) + (cert == ops.FIELD_FULL).to(torch.int32)
+        bins = torch.where(cert == ops.FIELD_CERTIFIED, fws["rounds"].clamp(max=rounds - 1), other)
+        counts.add_((bins[:, None] == bin_ids[None]).sum(0))          # (no bincount: its output size is a host look)
+
+    torch.cuda.synchronize(dev)
+    graph = None
+    if use_graph and not record:
+        tctr = torch.zeros(1, dtype=torch.long, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        saved = [v.clone() for v in state]
+        with torch.cuda.stream(side):
+            one_step(tctr)
+        side.synchronize()
+        for dst, src in zip(state, saved):
+            dst.copy_(src)
+        tctr.zero_()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            one_step(tctr)
+            tctr.add_(1)
+        for dst, src in zip(state, saved):
+            dst.copy_(src)
+        tctr.zero_()
+        torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter()
+    for t in range(numSteps):
+        if graph is not None:
+            graph.replay()
+        else:
+            one_step(t)
+        if record:
+            rec["traj"][t + 1] = x
+            rec["y"][t] = ws["y"]
+            rec["cert"][t], rec["rounds_rec"][t], rec["status_eff"][t] = fws["cert"], fws["rounds"], fws["status_eff"]
+            rec["idx"][t] = fws["idx"]
+    torch.cuda.synchronize(dev)
+    t_loop = time.perf_counter() - t_loop
+    min_h, cost, fails = fws["min_h"], fws["cost"], fws["fails"]
+    collided = ~(min_h >= 0)
+    stats = reduce_rollout_stats(collided.sum(), min_h.min(), cost.sum() / numSteps, (fails > 0).sum(), Bt)
+    c = counts.tolist()
+    out = dict(stats=stats, x_final=x, min_h=min_h, dist_to_goal=(x[:, :2] - xg[:2]).norm(dim=1), loop_seconds=t_loop,
+               certified_steps=sum(c[:rounds]), rounds_hist=c[:rounds], uncertified_steps=c[rounds], full_set_steps=c[rounds + 1],
+               unsolved_steps=c[rounds + 2], traj=None)
+    if record:
+        out.update(rec)
+    return out
+
+
 def _trigger_hyper(ls, sf, A, B, Bt, f):
     """ls, sf, A, B of one model or of Bt models -> dict(ls[Bh,3], sf[Bh], Adiag[Bh,3], B[Bh,3,3]) for the trigger step, Bh = 1 or Bt
     (mixed leading extents are expanded to Bt)."""

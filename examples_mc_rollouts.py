@@ -61,6 +61,24 @@ def self_triggered(args, ctx, gp, dtype, n_loc):
         print(json.dumps(line))
 
 
+def obstacle_field(args, ctx, gp, dtype, n_loc):
+    """--obstacle-field K: `rollouts.obstacle_field_rollouts` among K random discs (--field-seed)."""
+    from bayesian_cbf_amd.rollouts import obstacle_field_rollouts, random_obstacle_field
+    if ctx.world != 1 or args.plant != "true":
+        sys.exit("--obstacle-field runs on one GPU, on the true plant")
+    field = random_obstacle_field(args.obstacle_field, seed=args.field_seed)
+    out = obstacle_field_rollouts(n_loc, field, numSteps=args.steps, gp=gp, max_risk=args.max_risk, seed=ctx.rank, dtype=dtype,
+                                  device=ctx.device, use_graph=args.graph)
+    n = n_loc * args.steps
+    line = dict(config="c4 among an obstacle field: working set of three discs, certified against all", trajectories=n_loc,
+                steps=args.steps, discs=args.obstacle_field, field_seed=args.field_seed, loop_seconds=out["loop_seconds"],
+                trajectory_steps_per_s_loop_only=n / out["loop_seconds"], certified_steps=out["certified_steps"],
+                certified_share=out["certified_steps"] / n, rounds_hist=out["rounds_hist"], uncertified_steps=out["uncertified_steps"],
+                full_set_steps=out["full_set_steps"], unsolved_steps=out["unsolved_steps"], **out["stats"])
+    if ctx.rank == 0:
+        print(json.dumps(line))
+
+
 def self_triggered_learning(args, ctx, dtype, n_loc, dt):
     """--trigger self --learn: `rollouts.self_triggered_learning_rollouts`, the self-triggered loop on a model it refits from its own
     rows (start model: synthetic, --max-train points per trajectory; prior wheelbase 1 against a true 12)."""
@@ -120,6 +138,10 @@ def main():
     ap.add_argument("--predict-8gpu", action="store_true",
                     help="one GPU only: also time the per-GPU shape of the 8-way strong split (trajectories / 8) and print "
                          "predicted_strong_scaling_8gpu = loop(trajectories) / loop(trajectories / 8) -- what an 8-GPU node could gain")
+    ap.add_argument("--obstacle-field", type=int, default=0, metavar="K",
+                    help="K > 0: the periodic loop among a field of K random discs (up to 256) instead of the two mid obstacles -- a "
+                         "working set of three in the fused solver, certified against all K; one GPU; prints its own JSON line")
+    ap.add_argument("--field-seed", type=int, default=0, help="--obstacle-field: the seed of rollouts.random_obstacle_field")
     ap.add_argument("--dtype", choices=["f32", "f64"], default=None,
                     help="precision of the shared learned model (default: f64 as the reference's module for N <= 512, else f32)")
     args = ap.parse_args()
@@ -150,6 +172,10 @@ def main():
                                     p["M0"]).as_dict()
     if args.trigger == "self":
         self_triggered(args, ctx, gp, dtype, b - a)
+        ctx.close()
+        return
+    if args.obstacle_field:
+        obstacle_field(args, ctx, gp, dtype, b - a)
         ctx.close()
         return
     torch.cuda.synchronize()

@@ -1490,6 +1490,73 @@ int bcbf_unicycle_control_step_rbfm52_f64(
     double* Bk, double* cones, int* cstatus, double* y, int* status, int* iters, double dt, double L_true, int Bt,
     int N, int Kob, int max_iters, int shared_gp, void* ev_start, void* ev_stop, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Obstacle fields (obstacle_field.hip): the chance-constrained unicycle step of bcbf_unicycle_control_step among up to
+ * BCBF_MAX_FIELD discs, solved on a WORKING SET of S <= 3 of them in the fused kernel and certified against all of them.
+ * Reference: ObstacleCBF, unicycle_move_to_pose.py:618-696; one un-relaxed cone per obstacle (`_cbcs`, :901-920); the program
+ * (:926-953).  The program is convex and its objective strictly convex in (u, relax): a working-set optimum at which no other
+ * disc's cone is violated is feasible for the full program, hence its unique optimum.
+ * The field: centers_f[Bf,Kf,2], radii_f[Bf,Kf]; field_stride 0 = one field for every instance (Bf = 1), 1 = one per instance
+ * (Bf = Bt).  One gamma for the whole field.  1 <= S <= 3, S <= Kf <= BCBF_MAX_FIELD.  Both precisions carry the arithmetic
+ * in fp64 from the inputs as stored, so no decision depends on the entry's precision.  One wave per instance, lanes stride over
+ * the discs; no LDS, no scratch.
+ *
+ * bcbf_obstacle_field_select: h_k(x) = tw0 (|p - c_k|^2 - r_k^2) + tw1 heading_k (ObstacleCBF.cbf, :624-630) of every disc;
+ *   idx[Bt,S] = the S smallest (ties to the lower index, NaN below everything), centers_sel[Bt,S,2] / radii_sel[Bt,S] = their
+ *   discs -- the `centers` / `radii` the control step reads; min_h[Bt] = min(min_h, min_k h_k) in place (a non-finite h counts
+ *   as -inf); cert[Bt] = rounds[Bt] = 0.
+ * bcbf_obstacle_field_audit: x[Bt,3] the state the program was formed at (solve with dt = 0), y[Bt,3] = (u, relax) and
+ *   status[Bt] of the solve, Mk[Bt,3,3], Bk[Bt,3,3], A[Bt,3,3], fhat[Bt,3], ghat[Bt,3,2] as the control step exposes them,
+ *   rho[Bt].  Per instance:
+ *     cert != 0 on entry: nothing is touched (the call is idempotent);
+ *     status != BCBF_SOCP_OPTIMAL: cert = BCBF_FIELD_UNSOLVED (worst_margin = NaN, worst_idx = -1, nviol = 0);
+ *     else for every disc, with ubar = (1, u):  E_k = grad h_k . (fhat + ghat u + M_k ubar) + gamma h_k,
+ *       s_k = sqrt(max(ubar' B_k ubar  grad h_k' A grad h_k, 0)),  margin_k = E_k - rho s_k  (NaN counts as -inf) -- the cone of
+ *       cbc2_quadratic_terms -> convert_cbc_terms_to_socp_terms (:837-878); an UNSELECTED disc is a violator when
+ *       margin_k < -tol_f max(1, |E_k|, rho s_k).  worst_margin / worst_idx = the smallest margin among the unselected discs
+ *       (ties to the lower index; +inf / -1 when Kf = S), nviol = the number of violators.
+ *       No violator: cert = BCBF_FIELD_CERTIFIED.  Else the slot of largest margin (ties to the lower slot): when that margin is
+ *       <= tol_a max(1, |E|, rho s) every slot is active, cert = BCBF_FIELD_FULL; otherwise that slot's idx / centers_sel /
+ *       radii_sel are overwritten with the violator of smallest margin (ties to the lower index), rounds += 1, cert stays 0.
+ *     Dropping a slack cone keeps the optimum and adding a violated one strictly raises the optimal value: no cycling.
+ *   Tolerances: fp64 entries  tol_f = 1e-7 (the solvers' acceptance), tol_a = 1e-6;  fp32 entries, whose solver rows are
+ *   formed in fp32:  tol_f = BCBF_FIELD_TOL_F_F32, tol_a = BCBF_FIELD_TOL_A_F32 (measured).
+ * bcbf_obstacle_field_commit (one lane per instance): status_eff = 0 where cert == BCBF_FIELD_CERTIFIED, else status when
+ *   that is not 0, else BCBF_FIELD_UNCERTIFIED; where status_eff == 0 and dt > 0, x += g(x; L_true) u dt (:277-282).  Every
+ *   other instance keeps its state (the reference raises ValueError there, :954-964).
+ * BCBF_EINVAL with a reason in bcbf_last_error, before any HIP call, for: Bt <= 0, S outside 1..3, Kf outside S..BCBF_MAX_FIELD,
+ * field_stride not 0 / 1, a tolerance negative or not finite, any null pointer; commit: dt negative or not finite, L_true zero
+ * or not finite with dt > 0. */
+#define BCBF_MAX_FIELD 256
+#define BCBF_FIELD_CERTIFIED 1
+#define BCBF_FIELD_FULL 2
+#define BCBF_FIELD_UNSOLVED 3
+#define BCBF_FIELD_UNCERTIFIED 6   /* status_eff: solved on the working set, not certified against the field */
+#define BCBF_FIELD_TOL_F_F32 5e-7   /* 10 x 4.81e-8: the audit's fp32-stored margin against the float64 margin of the same inputs */
+#define BCBF_FIELD_TOL_A_F32 7e-6   /* 10 x 6.93e-7: the working set's active cones, rows formed in fp32, as the fp64 audit sees them */
+int bcbf_obstacle_field_select_f32(const float* x, const float* centers_f, const float* radii_f, int field_stride,
+                                   const float* tw, int* idx, float* centers_sel, float* radii_sel, float* min_h, int* cert,
+                                   int* rounds, int Bt, int Kf, int S, void* stream);
+int bcbf_obstacle_field_select_f64(const double* x, const double* centers_f, const double* radii_f, int field_stride,
+                                   const double* tw, int* idx, double* centers_sel, double* radii_sel, double* min_h,
+                                   int* cert, int* rounds, int Bt, int Kf, int S, void* stream);
+int bcbf_obstacle_field_audit_f32(const float* x, const float* y, const int* status, const float* Mk, const float* Bk,
+                                  const float* A, const float* fhat, const float* ghat, const float* rho,
+                                  const float* centers_f, const float* radii_f, int field_stride, const float* tw, float gamma,
+                                  double tol_f, double tol_a, int* idx, float* centers_sel, float* radii_sel, int* cert,
+                                  int* rounds, float* worst_margin, int* worst_idx, int* nviol, int Bt, int Kf, int S,
+                                  void* stream);
+int bcbf_obstacle_field_audit_f64(const double* x, const double* y, const int* status, const double* Mk, const double* Bk,
+                                  const double* A, const double* fhat, const double* ghat, const double* rho,
+                                  const double* centers_f, const double* radii_f, int field_stride, const double* tw,
+                                  double gamma, double tol_f, double tol_a, int* idx, double* centers_sel, double* radii_sel,
+                                  int* cert, int* rounds, double* worst_margin, int* worst_idx, int* nviol, int Bt, int Kf,
+                                  int S, void* stream);
+int bcbf_obstacle_field_commit_f32(float* x, const float* y, const int* status, const int* cert, int* status_eff, float dt,
+                                   float L_true, int Bt, void* stream);
+int bcbf_obstacle_field_commit_f64(double* x, const double* y, const int* status, const int* cert, int* status_eff, double dt,
+                                   double L_true, int Bt, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
