@@ -13,6 +13,23 @@ c_int, c_void_p, c_size_t = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
 c_float, c_double = ctypes.c_float, ctypes.c_double
 P = c_void_p
 
+# The control-step entries: a signature is a sum of named argument groups (csrc/control_step.hip, csrc/pendulum.hip), then
+# _STREAM = (ev_start, ev_stop, stream).  Unicycle: the 42 common arguments; (xq, obs_x, obs_uh, obs_y, obs_ld, xq_next, flags);
+# (kernel_kind, z, xdot_s, cbc_s).  Pendulum: the 56 common arguments (x_goal, Q_goal: HOST values); (prior, explore, eps,
+# ctrl_range (HOST), obs_x, obs_uh, obs_y, obs_ld); (z, xdot_s, cbc_s, relaxed, viol_relaxed, rho_tol); (nominal, numSteps, t,
+# t_dev, lstatus); (Bt, n, m).
+_STREAM = [P, P, P]
+_UNI_HEAD = [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T"] + [c_int] * 5
+_UNI_OBSERVE = [P, P, P, P, c_int, P, c_int]
+_UNI_SAMPLED = [c_int, P, P, P]
+_PD = ctypes.POINTER(c_double)
+_PEND_HEAD = ([P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, _PD, _PD, c_double, P] + [c_double] * 3 + [c_int] * 2 + [c_double] * 4
+              + [P] * 24)
+_PEND_LEARN = [c_int, P, c_double, _PD, P, P, P, c_int]
+_PEND_DRAW = [P] * 5 + [c_double]
+_PEND_NOMINAL = [c_int] * 3 + [P, P]
+_PEND_SIZES = [c_int] * 3
+
 # name -> (restype, argtypes); "{T}" entries are instantiated for f32 (c_float) and f64 (c_double)
 _SIGS = {
     "bcbf_version": (c_int, []),
@@ -34,27 +51,11 @@ _SIGS = {
     "bcbf_coneqp_f64": (c_int, [P, P, P, P, c_int, c_int, ctypes.POINTER(c_int), c_int, P, P, P, c_int, c_int, P]),
     # (is_f64, Bt, N, cus, has_Kdense, has_Ldense, kernel_kind, form) -> out_plan[4]: a host function, no device call
     "bcbf_refit_plan": (c_int, [c_int] * 8 + [ctypes.POINTER(c_int)]),
-    "bcbf_pendulum_control_step_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
-                                               ctypes.POINTER(c_double), c_double, P] + [c_double] * 3 + [c_int] * 2
-                                       + [c_double] * 4 + [P] * 24 + [c_int] * 3 + [P] * 3),
-    "bcbf_pendulum_control_step_observe_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
-                                                       ctypes.POINTER(c_double), c_double, P] + [c_double] * 3
-                                               + [c_int] * 2 + [c_double] * 4 + [P] * 24
-                                               + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
-                                               + [c_int] * 3 + [P] * 3),
-    # the observing entry's arguments, then (z, xdot_s, cbc_s, relaxed, viol_relaxed, rho_tol)
-    "bcbf_pendulum_control_step_sampled_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
-                                                       ctypes.POINTER(c_double), c_double, P] + [c_double] * 3
-                                               + [c_int] * 2 + [c_double] * 4 + [P] * 24
-                                               + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
-                                               + [P] * 5 + [c_double] + [c_int] * 3 + [P] * 3),
-    # the sampled entry's arguments, then (nominal, numSteps, t, t_dev, lstatus): LQRController in place of GreedyController
-    # (controllers.py:64-115, 681)
-    "bcbf_pendulum_control_step_nominal_f64": (c_int, [P] * 9 + [c_int] * 4 + [c_double] * 5 + [P, ctypes.POINTER(c_double),
-                                                       ctypes.POINTER(c_double), c_double, P] + [c_double] * 3
-                                               + [c_int] * 2 + [c_double] * 4 + [P] * 24
-                                               + [c_int, P, c_double, ctypes.POINTER(c_double), P, P, P, c_int]
-                                               + [P] * 5 + [c_double] + [c_int] * 3 + [P, P] + [c_int] * 3 + [P] * 3),
+    "bcbf_pendulum_control_step_f64": (c_int, _PEND_HEAD + _PEND_SIZES + _STREAM),
+    "bcbf_pendulum_control_step_observe_f64": (c_int, _PEND_HEAD + _PEND_LEARN + _PEND_SIZES + _STREAM),
+    "bcbf_pendulum_control_step_sampled_f64": (c_int, _PEND_HEAD + _PEND_LEARN + _PEND_DRAW + _PEND_SIZES + _STREAM),
+    # the nominal group: LQRController in place of GreedyController (controllers.py:64-115, 681)
+    "bcbf_pendulum_control_step_nominal_f64": (c_int, _PEND_HEAD + _PEND_LEARN + _PEND_DRAW + _PEND_NOMINAL + _PEND_SIZES + _STREAM),
 }
 # the trigger-step entries: the event's 35 arguments, the 19 of the audit group, the 9 of the observe group, (Bt, Bh, Kob, Nte, P, stream)
 _TS_EVENT = [P] * 9 + [c_double] + [P] * 4 + [c_double] * 6 + ["T", P, P, c_double] + [P] * 11
@@ -74,10 +75,8 @@ _TSIGS = {
     "bcbf_refit_retry_kind": [P] * 10 + [c_int, c_int, c_int, c_int, c_int, P],
     "bcbf_gram": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bcbf_predict_fullmat": [P] * 17 + [c_int] * 5 + [P],
-    "bcbf_unicycle_control_step_observe": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int,
-                                           P, P, P, P, c_int, P, c_int, P, P, P],
-    "bcbf_unicycle_control_step_sampled": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int,
-                                           P, P, P, P, c_int, P, c_int, c_int, P, P, P, P, P, P],
+    "bcbf_unicycle_control_step_observe": _UNI_HEAD + _UNI_OBSERVE + _STREAM,
+    "bcbf_unicycle_control_step_sampled": _UNI_HEAD + _UNI_OBSERVE + _UNI_SAMPLED + _STREAM,
     "bcbf_rollout_risk": [P, P, P, P, P, c_int, c_int, P],
     "bcbf_potrf": [P, P, P, P, c_int, c_int, P],
     "bcbf_subsample_rows": [P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P],
@@ -147,9 +146,9 @@ _TSIGS = {
     "bcbf_obstacle_field_audit": [P] * 11 + [c_int, P, "T", c_double, c_double] + [P] * 8 + [c_int] * 3 + [P],
     "bcbf_obstacle_field_commit": [P] * 5 + ["T", "T", c_int, P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],
-    "bcbf_unicycle_control_step": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
-    "bcbf_unicycle_control_step_matern52": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
-    "bcbf_unicycle_control_step_rbfm52": [P] * 13 + ["T"] + [P] * 4 + ["T"] + [P] * 16 + ["T", "T", c_int, c_int, c_int, c_int, c_int, P, P, P],
+    "bcbf_unicycle_control_step": _UNI_HEAD + _STREAM,
+    "bcbf_unicycle_control_step_matern52": _UNI_HEAD + _STREAM,
+    "bcbf_unicycle_control_step_rbfm52": _UNI_HEAD + _STREAM,
 }
 
 

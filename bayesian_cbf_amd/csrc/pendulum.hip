@@ -293,45 +293,67 @@ static int pendulum_einval(const char* why) {
     return BCBF_EINVAL;
 }
 
+// The 56 arguments every control-step entry takes, then (Bt, n, m) and the stream triple: in ABI order (include/bcbf.h)
+struct PendulumStepArgs {
+    const double *Lop, *Vw, *X, *UHB, *ell, *s2, *Bm, *M0, *A;
+    int N, shared, kernel_kind, mean_model;
+    double mean_mass, mean_gravity, mean_length, theta_c, delta_c;
+    const double *kalpha, *x_goal, *Q_goal;
+    double R;
+    const double* u_ref_in;
+    double safety_factor, ctrl_reg, relax_weight;
+    int hessian_mode, max_iters;
+    double true_mass, true_gravity, true_length, dt;
+    double *x, *Mk, *Bk, *G, *Mj, *h, *gh, *Hh, *u_ref, *terms2, *terms;
+    int* tstatus;
+    double *Gc, *hc;
+    int* cstatus;
+    double *P, *q, *y;
+    int *sstatus, *iters;
+    double* u;
+    int* status;
+    double* min_h;
+    int* fails;
+    int Bt, n, m;
+    void *ev_start, *ev_stop, *stream;
+};
+
+// Lg: the observing entries' own arguments (pendulum_learn_args); D, Nm: NULL without the sampled / nominal group
 template <bool Learn>
-static int pendulum_control_step(
-    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
-    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
-    int mean_model, double mean_mass, double mean_gravity, double mean_length,
-    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
-    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
-    double true_mass, double true_gravity, double true_length, double dt,
-    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
-    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
-    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
-    const PendulumLearn<double>& L, const PendulumDraw<double>* D, int Bt, int n, int m, void* ev_start, void* ev_stop,
-    void* stream, const PendulumNominal* Nm = nullptr) {
+static int pendulum_control_step(const PendulumStepArgs& a, const PendulumLearn<double>& Lg, const PendulumDraw<double>* D = nullptr,
+                                 const PendulumNominal* Nm = nullptr) {
+    PendulumLearn<double> L = Lg;
+    if (Learn) {      // what the Learn = true kernels read of the common arguments
+        L.M0 = a.M0; L.s2 = a.s2; L.Bm = a.Bm;
+        L.has_mean = a.mean_model != 0;
+        L.mean_mass = a.mean_mass; L.mean_gravity = a.mean_gravity; L.mean_length = a.mean_length;
+    }
     // ---- argument checks, before any HIP call
-    if (Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
-    if (n != 2 || m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
-    if (!x || !ell || !s2 || !Bm || !A || !kalpha || !x_goal || !Q_goal)
+    if (a.Bt < 0) return pendulum_einval("pendulum_control_step: Bt < 0");
+    if (a.n != 2 || a.m != 1) return pendulum_einval("pendulum_control_step: the pendulum has n = 2, m = 1");
+    if (!a.x || !a.ell || !a.s2 || !a.Bm || !a.A || !a.kalpha || !a.x_goal || !a.Q_goal)
         return pendulum_einval("pendulum_control_step: null state / model / task buffer");
-    if (!Mk || !Bk || !G || !Mj || !h || !gh || !Hh || !u_ref || !terms2 || !terms || !tstatus || !Gc || !hc ||
-        !cstatus || !P || !q || !y || !sstatus || !u || !status)
+    if (!a.Mk || !a.Bk || !a.G || !a.Mj || !a.h || !a.gh || !a.Hh || !a.u_ref || !a.terms2 || !a.terms || !a.tstatus || !a.Gc ||
+        !a.hc || !a.cstatus || !a.P || !a.q || !a.y || !a.sstatus || !a.u || !a.status)
         return pendulum_einval("pendulum_control_step: null workspace buffer");
-    if (!min_h != !fails) return pendulum_einval("pendulum_control_step: min_h and fails go together");
-    if (Lop && (!Vw || !X || !UHB || !M0 || N < 1)) return pendulum_einval("pendulum_control_step: incomplete GP");
-    if (shared != 0 && shared != 1) return pendulum_einval("pendulum_control_step: shared must be 0 or 1");
-    if (kernel_kind < 0 || kernel_kind >= BCBF_KINDS) return pendulum_einval("pendulum_control_step: bad kernel_kind");
-    if (hessian_mode != 0 && hessian_mode != 1) return pendulum_einval("pendulum_control_step: bad hessian_mode");
-    if (max_iters < 1) return pendulum_einval("pendulum_control_step: max_iters < 1");
-    if (!(dt > 0.0) || !(R > 0.0)) return pendulum_einval("pendulum_control_step: dt and R must be > 0");
-    if (mean_model && !(mean_mass * mean_length != 0.0)) return pendulum_einval("pendulum_control_step: mean model m l == 0");
-    if (!(true_mass * true_length != 0.0)) return pendulum_einval("pendulum_control_step: true model m l == 0");
-    if (!(safety_factor >= 0.0) || !(ctrl_reg > 0.0) || !(relax_weight > 0.0))
+    if (!a.min_h != !a.fails) return pendulum_einval("pendulum_control_step: min_h and fails go together");
+    if (a.Lop && (!a.Vw || !a.X || !a.UHB || !a.M0 || a.N < 1)) return pendulum_einval("pendulum_control_step: incomplete GP");
+    if (a.shared != 0 && a.shared != 1) return pendulum_einval("pendulum_control_step: shared must be 0 or 1");
+    if (a.kernel_kind < 0 || a.kernel_kind >= BCBF_KINDS) return pendulum_einval("pendulum_control_step: bad kernel_kind");
+    if (a.hessian_mode != 0 && a.hessian_mode != 1) return pendulum_einval("pendulum_control_step: bad hessian_mode");
+    if (a.max_iters < 1) return pendulum_einval("pendulum_control_step: max_iters < 1");
+    if (!(a.dt > 0.0) || !(a.R > 0.0)) return pendulum_einval("pendulum_control_step: dt and R must be > 0");
+    if (a.mean_model && !(a.mean_mass * a.mean_length != 0.0)) return pendulum_einval("pendulum_control_step: mean model m l == 0");
+    if (!(a.true_mass * a.true_length != 0.0)) return pendulum_einval("pendulum_control_step: true model m l == 0");
+    if (!(a.safety_factor >= 0.0) || !(a.ctrl_reg > 0.0) || !(a.relax_weight > 0.0))
         return pendulum_einval("pendulum_control_step: safety factor, ctrl_reg, relax_weight");
     if (Learn) {
         if (L.prior != 0 && L.prior != 1) return pendulum_einval("pendulum_control_step_observe: prior must be 0 or 1");
-        if (!Lop && L.prior && (!L.M0 || !L.s2 || !L.Bm))
+        if (!a.Lop && L.prior && (!L.M0 || !L.s2 || !L.Bm))
             return pendulum_einval("pendulum_control_step_observe: the prior needs M0");
         if (!(L.eps >= 0.0 && L.eps <= 1.0)) return pendulum_einval("pendulum_control_step_observe: eps must lie in [0, 1]");
         if (L.explore && !L.clip) return pendulum_einval("pendulum_control_step_observe: explore needs ctrl_range");
-        if (L.explore && u_ref_in) return pendulum_einval("pendulum_control_step_observe: explore wraps the greedy u_ref, not u_ref_in");
+        if (L.explore && a.u_ref_in) return pendulum_einval("pendulum_control_step_observe: explore wraps the greedy u_ref, not u_ref_in");
         if (L.clip && !(L.lo <= L.hi)) return pendulum_einval("pendulum_control_step_observe: ctrl_range needs lo <= hi");
         if ((L.obs_x || L.obs_uh || L.obs_y) && (!L.obs_x || !L.obs_uh || !L.obs_y))
             return pendulum_einval("pendulum_control_step_observe: obs_x, obs_uh, obs_y go together");
@@ -348,87 +370,83 @@ static int pendulum_control_step(
     const bool lqr = Nm && Nm->nominal == 1;
     if (Nm) {
         if (Nm->nominal != 0 && Nm->nominal != 1) return pendulum_einval("pendulum_control_step_nominal: nominal must be 0 or 1");
-        if (lqr && u_ref_in) return pendulum_einval("pendulum_control_step_nominal: the LQR nominal control excludes u_ref_in");
+        if (lqr && a.u_ref_in) return pendulum_einval("pendulum_control_step_nominal: the LQR nominal control excludes u_ref_in");
         if (lqr && !Nm->lstatus) return pendulum_einval("pendulum_control_step_nominal: the LQR nominal control needs lstatus");
         if (lqr && Nm->numSteps < 1) return pendulum_einval("pendulum_control_step_nominal: numSteps < 1");
         if (lqr && !Nm->t_dev && Nm->t < 0) return pendulum_einval("pendulum_control_step_nominal: t < 0 without t_dev");
     }
-    if (Bt == 0) return BCBF_OK;
-    hipStream_t st = (hipStream_t)stream;
+    if (a.Bt == 0) return BCBF_OK;
+    hipStream_t st = (hipStream_t)a.stream;
     // 1. jets of the learned model at x (skipped without one: the task kernel writes the mean model alone)
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+    if (a.ev_start) (void)hipEventRecord((hipEvent_t)a.ev_start, st);
     int rc = BCBF_OK;
-    if (Lop) {
-        auto jets = kernel_kind == 0 ? bcbf_posterior_jets_f64 : kernel_kind == 1 ? bcbf_posterior_jets_matern52_f64
+    if (a.Lop) {
+        auto jets = a.kernel_kind == 0 ? bcbf_posterior_jets_f64 : a.kernel_kind == 1 ? bcbf_posterior_jets_matern52_f64
                                                                                   : bcbf_posterior_jets_rbfm52_f64;
-        rc = jets(Lop, Vw, X, UHB, ell, s2, Bm, M0, x, Mk, Bk, G, Mj, nullptr, shared, Bt, N, 2, 1, stream);
+        rc = jets(a.Lop, a.Vw, a.X, a.UHB, a.ell, a.s2, a.Bm, a.M0, a.x, a.Mk, a.Bk, a.G, a.Mj, nullptr, a.shared, a.Bt, a.N, 2, 1,
+                  a.stream);
     }
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+    if (a.ev_stop) (void)hipEventRecord((hipEvent_t)a.ev_stop, st);
     if (rc) return rc;
     // 2. task kernel
     PendulumParams<double> p;
-    p.has_gp = Lop != nullptr;
-    p.has_mean = mean_model != 0;
-    p.has_uref = u_ref_in != nullptr;
-    p.mean_mass = mean_mass; p.mean_gravity = mean_gravity; p.mean_length = mean_length;
-    p.theta_c = theta_c; p.delta_c = delta_c;
-    p.xg[0] = x_goal[0]; p.xg[1] = x_goal[1];
-    for (int i = 0; i < 4; ++i) p.Qg[i] = Q_goal[i];
-    p.R = R; p.dt = dt;
-    const dim3 grid((Bt + 255) / 256), block(256);
-    hipLaunchKernelGGL((pendulum_task_kernel<double, Learn>), grid, block, 0, st, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref_in,
-                       u_ref, P, q, p, L, Bt);
+    p.has_gp = a.Lop != nullptr;
+    p.has_mean = a.mean_model != 0;
+    p.has_uref = a.u_ref_in != nullptr;
+    p.mean_mass = a.mean_mass; p.mean_gravity = a.mean_gravity; p.mean_length = a.mean_length;
+    p.theta_c = a.theta_c; p.delta_c = a.delta_c;
+    p.xg[0] = a.x_goal[0]; p.xg[1] = a.x_goal[1];
+    for (int i = 0; i < 4; ++i) p.Qg[i] = a.Q_goal[i];
+    p.R = a.R; p.dt = a.dt;
+    const dim3 grid((a.Bt + 255) / 256), block(256);
+    hipLaunchKernelGGL((pendulum_task_kernel<double, Learn>), grid, block, 0, st, a.x, a.Mk, a.Bk, a.G, a.Mj, a.h, a.gh, a.Hh,
+                       a.u_ref_in, a.u_ref, a.P, a.q, p, L, a.Bt);
     if ((rc = check_launch("pendulum_task"))) return rc;
     // 2b. LQRController in place of the task kernel's greedy u_ref, on the factors it has just shifted: bcbf_lqr_nominal_f64's
     // kernel, then the explorer's draw and the clip as the task kernel applies them
-    if (lqr && (rc = lqr_nominal_step_f64(Mk, Mj, x, x_goal, Q_goal, R, dt, Nm->numSteps, Nm->t, Nm->t_dev, L.explore, L.eps,
-                                          L.clip, L.lo, L.hi, u_ref, Nm->lstatus, Bt, stream)))
+    if (lqr && (rc = lqr_nominal_step_f64(a.Mk, a.Mj, a.x, a.x_goal, a.Q_goal, a.R, a.dt, Nm->numSteps, Nm->t, Nm->t_dev, L.explore,
+                                          L.eps, L.clip, L.lo, L.hi, a.u_ref, Nm->lstatus, a.Bt, a.stream)))
         return rc;
     // 3. rel-degree-2 terms (linearised at u_ref), 4. the program's rows (objective cone + safety cone of kind 1)
-    if ((rc = bcbf_cbc2_terms_f64(Mk, Bk, G, Mj, A, Bm, ell, s2, h, gh, Hh, kalpha, u_ref, terms2, tstatus, Bt, 2, 1,
-                                  hessian_mode, kernel_kind, stream)))
+    if ((rc = bcbf_cbc2_terms_f64(a.Mk, a.Bk, a.G, a.Mj, a.A, a.Bm, a.ell, a.s2, a.h, a.gh, a.Hh, a.kalpha, a.u_ref, a.terms2,
+                                  a.tstatus, a.Bt, 2, 1, a.hessian_mode, a.kernel_kind, a.stream)))
         return rc;
-    hipLaunchKernelGGL((pendulum_pack_terms_kernel<double>), grid, block, 0, st, terms2, terms, Bt);
+    hipLaunchKernelGGL((pendulum_pack_terms_kernel<double>), grid, block, 0, st, a.terms2, a.terms, a.Bt);
     if ((rc = check_launch("pendulum_pack_terms"))) return rc;
     const int kind = 1;
-    if ((rc = bcbf_controller_cones_f64(terms, u_ref, &kind, &safety_factor, ctrl_reg, relax_weight, 2, 1, Gc, hc,
-                                        cstatus, Bt, 1, 1, stream)))
+    if ((rc = bcbf_controller_cones_f64(a.terms, a.u_ref, &kind, &a.safety_factor, a.ctrl_reg, a.relax_weight, 2, 1, a.Gc, a.hc,
+                                        a.cstatus, a.Bt, 1, 1, a.stream)))
         return rc;
     // 5. min y_1 over y = [y_1, rho, u] in Q^3 x Q^3
     const int qdims[2] = {3, 3};
-    if ((rc = bcbf_coneqp_f64(P, q, Gc, hc, 3, 0, qdims, 2, y, sstatus, iters, Bt, max_iters, stream))) return rc;
+    if ((rc = bcbf_coneqp_f64(a.P, a.q, a.Gc, a.hc, 3, 0, qdims, 2, a.y, a.sstatus, a.iters, a.Bt, a.max_iters, a.stream))) return rc;
     // 6. choose u, bookkeeping, plant step (the sampled entry: on a draw from the model's posterior at x_t)
     if (D) {
         PendulumDraw<double> d = *D;
-        d.gp = Lop != nullptr || (Learn && L.prior);
-        d.kernel_kind = kernel_kind;
-        d.Mk = Mk; d.Bk = Bk; d.G = G; d.Mj = Mj; d.A = A; d.Bm = Bm; d.ell = ell; d.s2 = s2; d.gh = gh; d.Hh = Hh;
-        d.kalpha = kalpha;
-        hipLaunchKernelGGL((pendulum_sampled_plant_kernel<double>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
-                           h, u, status, min_h, fails, dt, L, d, Bt);
+        d.gp = a.Lop != nullptr || (Learn && L.prior);
+        d.kernel_kind = a.kernel_kind;
+        d.Mk = a.Mk; d.Bk = a.Bk; d.G = a.G; d.Mj = a.Mj; d.A = a.A; d.Bm = a.Bm; d.ell = a.ell; d.s2 = a.s2; d.gh = a.gh;
+        d.Hh = a.Hh; d.kalpha = a.kalpha;
+        hipLaunchKernelGGL((pendulum_sampled_plant_kernel<double>), grid, block, 0, st, a.x, a.y, a.sstatus, a.cstatus, a.tstatus,
+                           a.u_ref, a.h, a.u, a.status, a.min_h, a.fails, a.dt, L, d, a.Bt);
         return check_launch("pendulum_sampled_plant");
     }
-    hipLaunchKernelGGL((pendulum_plant_kernel<double, Learn>), grid, block, 0, st, x, y, sstatus, cstatus, tstatus, u_ref,
-                       h, u, status, min_h, fails, true_mass, true_gravity, true_length, dt, L, Bt);
+    hipLaunchKernelGGL((pendulum_plant_kernel<double, Learn>), grid, block, 0, st, a.x, a.y, a.sstatus, a.cstatus, a.tstatus, a.u_ref,
+                       a.h, a.u, a.status, a.min_h, a.fails, a.true_mass, a.true_gravity, a.true_length, a.dt, L, a.Bt);
     return check_launch("pendulum_plant");
 }
 
-// the observing entries' arguments as the kernels take them
-static PendulumLearn<double> pendulum_learn_args(const double* M0, const double* s2, const double* Bm, int mean_model,
-                                                 double mean_mass, double mean_gravity, double mean_length, int prior,
-                                                 const double* explore, double eps, const double* ctrl_range, double* obs_x,
-                                                 double* obs_uh, double* obs_y, int obs_ld) {
+// the observing entries' own arguments as the kernels take them (pendulum_control_step adds what it reads of the common ones)
+static PendulumLearn<double> pendulum_learn_args(int prior, const double* explore, double eps, const double* ctrl_range,
+                                                 double* obs_x, double* obs_uh, double* obs_y, int obs_ld) {
     PendulumLearn<double> L{};
     L.prior = prior;
-    L.M0 = M0; L.s2 = s2; L.Bm = Bm;
     L.explore = explore;
     L.eps = eps;
     L.clip = ctrl_range != nullptr;
     L.lo = ctrl_range ? ctrl_range[0] : 0.0;
     L.hi = ctrl_range ? ctrl_range[1] : 0.0;
     L.obs_x = obs_x; L.obs_uh = obs_uh; L.obs_y = obs_y; L.obs_ld = obs_ld;
-    L.has_mean = mean_model != 0;
-    L.mean_mass = mean_mass; L.mean_gravity = mean_gravity; L.mean_length = mean_length;
     return L;
 }
 
@@ -448,93 +466,48 @@ BCBF_PEND_PLANT(float, f32)
 BCBF_PEND_PLANT(double, f64)
 #undef BCBF_PEND_PLANT
 
-int bcbf_pendulum_control_step_f64(
-    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
-    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
-    int mean_model, double mean_mass, double mean_gravity, double mean_length,
-    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
-    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
-    double true_mass, double true_gravity, double true_length, double dt,
-    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
-    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
-    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
-    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
-    const bcbf::PendulumLearn<double> L{};
-    return bcbf::pendulum_control_step<false>(
-        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
-        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
-        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
-        P, q, y, sstatus, iters, u, status, min_h, fails, L, nullptr, Bt, n, m, ev_start, ev_stop, stream);
+// the parameters of each argument group, in ABI order (include/bcbf.h), and the records they fill
+#define BCBF_PEND_PARAMS                                                                                              \
+    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,     \
+        const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind, int mean_model,      \
+        double mean_mass, double mean_gravity, double mean_length, double theta_c, double delta_c, const double* kalpha, \
+        const double* x_goal, const double* Q_goal, double R, const double* u_ref_in, double safety_factor,           \
+        double ctrl_reg, double relax_weight, int hessian_mode, int max_iters, double true_mass, double true_gravity, \
+        double true_length, double dt, double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, \
+        double* Hh, double* u_ref, double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, \
+        double* P, double* q, double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails
+#define BCBF_PEND_TAIL int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream
+#define BCBF_PEND_ARGS                                                                                                \
+    bcbf::PendulumStepArgs {                                                                                          \
+        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length, theta_c, \
+            delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,  \
+            true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc,  \
+            cstatus, P, q, y, sstatus, iters, u, status, min_h, fails, Bt, n, m, ev_start, ev_stop, stream            \
+    }
+#define BCBF_PEND_LEARN_PARAMS                                                                                        \
+    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y, int obs_ld
+#define BCBF_PEND_LEARN_ARGS bcbf::pendulum_learn_args(prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld)
+#define BCBF_PEND_DRAW_PARAMS const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol
+#define BCBF_PEND_DRAW_ARGS bcbf::PendulumDraw<double> { z, xdot_s, cbc_s, relaxed, viol_relaxed, rho_tol }
+
+int bcbf_pendulum_control_step_f64(BCBF_PEND_PARAMS, BCBF_PEND_TAIL) {
+    return bcbf::pendulum_control_step<false>(BCBF_PEND_ARGS, bcbf::PendulumLearn<double>{});
 }
 
-int bcbf_pendulum_control_step_observe_f64(
-    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
-    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
-    int mean_model, double mean_mass, double mean_gravity, double mean_length,
-    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
-    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
-    double true_mass, double true_gravity, double true_length, double dt,
-    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
-    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
-    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
-    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
-    int obs_ld, int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
-    const bcbf::PendulumLearn<double> L = bcbf::pendulum_learn_args(M0, s2, Bm, mean_model, mean_mass, mean_gravity, mean_length,
-                                                                    prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld);
-    return bcbf::pendulum_control_step<true>(
-        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
-        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
-        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
-        P, q, y, sstatus, iters, u, status, min_h, fails, L, nullptr, Bt, n, m, ev_start, ev_stop, stream);
+int bcbf_pendulum_control_step_observe_f64(BCBF_PEND_PARAMS, BCBF_PEND_LEARN_PARAMS, BCBF_PEND_TAIL) {
+    return bcbf::pendulum_control_step<true>(BCBF_PEND_ARGS, BCBF_PEND_LEARN_ARGS);
 }
 
-int bcbf_pendulum_control_step_sampled_f64(
-    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
-    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
-    int mean_model, double mean_mass, double mean_gravity, double mean_length,
-    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
-    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
-    double true_mass, double true_gravity, double true_length, double dt,
-    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
-    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
-    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
-    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
-    int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
-    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
-    const bcbf::PendulumLearn<double> L = bcbf::pendulum_learn_args(M0, s2, Bm, mean_model, mean_mass, mean_gravity, mean_length,
-                                                                    prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld);
-    bcbf::PendulumDraw<double> D{};
-    D.z = z; D.xdot_s = xdot_s; D.cbc_s = cbc_s; D.relaxed = relaxed; D.viol_relaxed = viol_relaxed; D.rho_tol = rho_tol;
-    return bcbf::pendulum_control_step<true>(
-        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
-        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
-        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
-        P, q, y, sstatus, iters, u, status, min_h, fails, L, &D, Bt, n, m, ev_start, ev_stop, stream);
+int bcbf_pendulum_control_step_sampled_f64(BCBF_PEND_PARAMS, BCBF_PEND_LEARN_PARAMS, BCBF_PEND_DRAW_PARAMS, BCBF_PEND_TAIL) {
+    const bcbf::PendulumDraw<double> D = BCBF_PEND_DRAW_ARGS;
+    return bcbf::pendulum_control_step<true>(BCBF_PEND_ARGS, BCBF_PEND_LEARN_ARGS, &D);
 }
 
-int bcbf_pendulum_control_step_nominal_f64(
-    const double* Lop, const double* Vw, const double* X, const double* UHB, const double* ell, const double* s2,
-    const double* Bm, const double* M0, const double* A, int N, int shared, int kernel_kind,
-    int mean_model, double mean_mass, double mean_gravity, double mean_length,
-    double theta_c, double delta_c, const double* kalpha, const double* x_goal, const double* Q_goal, double R,
-    const double* u_ref_in, double safety_factor, double ctrl_reg, double relax_weight, int hessian_mode, int max_iters,
-    double true_mass, double true_gravity, double true_length, double dt,
-    double* x, double* Mk, double* Bk, double* G, double* Mj, double* h, double* gh, double* Hh, double* u_ref,
-    double* terms2, double* terms, int* tstatus, double* Gc, double* hc, int* cstatus, double* P, double* q,
-    double* y, int* sstatus, int* iters, double* u, int* status, double* min_h, int* fails,
-    int prior, const double* explore, double eps, const double* ctrl_range, double* obs_x, double* obs_uh, double* obs_y,
-    int obs_ld, const double* z, double* xdot_s, double* cbc_s, int* relaxed, int* viol_relaxed, double rho_tol,
-    int nominal, int numSteps, int t, const int* t_dev, int* lstatus,
-    int Bt, int n, int m, void* ev_start, void* ev_stop, void* stream) {
-    const bcbf::PendulumLearn<double> L = bcbf::pendulum_learn_args(M0, s2, Bm, mean_model, mean_mass, mean_gravity, mean_length,
-                                                                    prior, explore, eps, ctrl_range, obs_x, obs_uh, obs_y, obs_ld);
-    bcbf::PendulumDraw<double> D{};
-    D.z = z; D.xdot_s = xdot_s; D.cbc_s = cbc_s; D.relaxed = relaxed; D.viol_relaxed = viol_relaxed; D.rho_tol = rho_tol;
+// (no draws z: the observing entry's plant kernel)
+int bcbf_pendulum_control_step_nominal_f64(BCBF_PEND_PARAMS, BCBF_PEND_LEARN_PARAMS, BCBF_PEND_DRAW_PARAMS, int nominal, int numSteps,
+                                           int t, const int* t_dev, int* lstatus, BCBF_PEND_TAIL) {
+    const bcbf::PendulumDraw<double> D = BCBF_PEND_DRAW_ARGS;
     const bcbf::PendulumNominal Nm{nominal, numSteps, t, t_dev, lstatus};
-    return bcbf::pendulum_control_step<true>(
-        Lop, Vw, X, UHB, ell, s2, Bm, M0, A, N, shared, kernel_kind, mean_model, mean_mass, mean_gravity, mean_length,
-        theta_c, delta_c, kalpha, x_goal, Q_goal, R, u_ref_in, safety_factor, ctrl_reg, relax_weight, hessian_mode, max_iters,
-        true_mass, true_gravity, true_length, dt, x, Mk, Bk, G, Mj, h, gh, Hh, u_ref, terms2, terms, tstatus, Gc, hc, cstatus,
-        P, q, y, sstatus, iters, u, status, min_h, fails, L, z ? &D : nullptr, Bt, n, m, ev_start, ev_stop, stream, &Nm);
+    return bcbf::pendulum_control_step<true>(BCBF_PEND_ARGS, BCBF_PEND_LEARN_ARGS, z ? &D : nullptr, &Nm);
 }
 }

@@ -1150,6 +1150,22 @@ def rollout_stats(cst, y, status, w, gammas, min_h, cost, fails):
                                                          _p(fails), Bt, Kob, y.shape[1], _stream(cst)), "bcbf_rollout_stats")
 
 
+def _bind_call(fn, what, x, stream, out):
+    """What every bound step does per call: `call(ev_start, ev_stop, args)` runs fn(*args, ev_start, ev_stop, stream) -- on `stream`
+    when one was fixed, else on the current stream at call time -- checks the return code under the entry's name and returns `out`."""
+    dev = x.device
+    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+
+    def call(ev_start, ev_stop, args):
+        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
+        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
+        rc = fn(*args, ev0, ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc:
+            check(rc, what)
+        return out
+    return call
+
+
 def _control_step_args(gp, task, ws, x):
     """Argument checks shared by the two forms below: returns (gp with every key present, A[Bt,n,n], N, shared)."""
     Bt = x.shape[0]
@@ -1239,10 +1255,7 @@ def unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=1.0, L_mean=1.
         raise ValueError("gp['kernel'] must be one of %s" % (DATA_KERNELS,))
     if observe is not None and kernel != "rbf" and sampled is None:
         raise NotImplementedError("the observing control step is built for the reference's RBF data kernel")
-    if sampled is not None:
-        return _control_step_sampled_closure(gp, task, ws, x, A, N, shared, kernel, dt, L_true, L_mean, clf_gamma, max_iters,
-                                             stream, observe, sampled)
-    fn = getattr(lib, ("bcbf_unicycle_control_step_observe" if observe is not None else "bcbf_unicycle_control_step" + _KSUF[kernel]) + _suf(x))
+    name = "bcbf_unicycle_control_step" + ("_sampled" if sampled is not None else "_observe" if observe is not None else _KSUF[kernel])
     head = (_p(gp["Lop"]), _p(gp["Vw"]), _p(gp["X"]), _p(gp["UHB"]), _p(gp["ell"]), _p(gp["s2"]), _p(gp["Bm"]),
             _p(gp["M0"]), _p(A), _p(x), _p(task["plan"]), _p(task["dot_plan"]), _p(task["Kp"]), clf_gamma,
             _p(task["centers"]), _p(task["radii"]), _p(task["tw"]), _p(task["gammas"]), L_mean, _p(task["w"]),
@@ -1250,77 +1263,32 @@ def unicycle_control_step_prepare(gp, task, ws, x, dt=0.0, L_true=1.0, L_mean=1.
             _p(ws["fhat"]), _p(ws["ghat"]), _p(ws["Mk"]), _p(ws["Bk"]), _p(ws["cones"]), _p(ws["cstatus"]), _p(ws["y"]),
             _p(ws["status"]), _p(ws["iters"]), dt, L_true, Bt, N, Kob, max_iters, 1 if shared else 0)
     keep = (dict(gp), dict(task), dict(ws), x, A, stream, observe)      # the pointers above are only valid while these live
-    dev, y = x.device, ws["y"]
-    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-
-    if observe is not None:
-        xq, xq_next = observe.get("xq"), observe.get("xq_next")
-        _chk(x, xq, xq_next)
-        p_xq, p_next = _p(xq), _p(xq_next)
-        si = (1 if observe.get("shift_invariant", True) else 0) | (2 if observe.get("advance_plan", False) else 0)   # the entry's `flags`
-
-        def step(ev_start=None, ev_stop=None, obs=None):
-            ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
-            ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
-            if obs is None:
-                o = (None, None, None, 1)
-            else:
-                o = (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
-            rc = fn(*head, p_xq, *o, p_next, si, ev0, ev1,
-                    fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc:
-                check(rc, "bcbf_unicycle_control_step_observe")
-            return y
+    call = _bind_call(getattr(lib, name + _suf(x)), name, x, stream, ws["y"])
+    if observe is None and sampled is None:
+        def step(ev_start=None, ev_stop=None):
+            return call(ev_start, ev_stop, head)
         step.keep = keep
         return step
 
-    def step(ev_start=None, ev_stop=None):
-        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
-        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
-        rc = fn(*head, ev0, ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc:
-            check(rc, "bcbf_unicycle_control_step")
-        return y
-    step.keep = keep
-    return step
-
-
-def _control_step_sampled_closure(gp, task, ws, x, A, N, shared, kernel, dt, L_true, L_mean, clf_gamma, max_iters, stream,
-                                  observe, sampled):
-    """`unicycle_control_step_prepare(sampled=...)`: the same closure form and pointer caching on the sampled entry point."""
-    Bt, Kob = x.shape[0], task["centers"].shape[1]
-    z, xdot_s, cbc_s = sampled["z"], sampled.get("xdot_s"), sampled.get("cbc_s")
-    _chk(x, z, xdot_s, cbc_s)
-    if z is None or tuple(z.shape) != (Bt, 3):
-        raise ValueError("sampled['z'] must be a [Bt,3] tensor of standard-normal draws")
-    if (xdot_s is not None and tuple(xdot_s.shape) != (Bt, 3)) or (cbc_s is not None and tuple(cbc_s.shape) != (Bt, 1 + Kob)):
-        raise ValueError("sampled['xdot_s'] is [Bt,3] and sampled['cbc_s'] is [Bt,1+Kob]")
-    fn = getattr(lib, "bcbf_unicycle_control_step_sampled" + _suf(x))
-    head = (_p(gp["Lop"]), _p(gp["Vw"]), _p(gp["X"]), _p(gp["UHB"]), _p(gp["ell"]), _p(gp["s2"]), _p(gp["Bm"]),
-            _p(gp["M0"]), _p(A), _p(x), _p(task["plan"]), _p(task["dot_plan"]), _p(task["Kp"]), clf_gamma,
-            _p(task["centers"]), _p(task["radii"]), _p(task["tw"]), _p(task["gammas"]), L_mean, _p(task["w"]),
-            _p(task["r"]), _p(task["sign"]), _p(task["relax_mask"]), _p(task["rho"]), _p(ws["grad"]), _p(ws["cst"]),
-            _p(ws["fhat"]), _p(ws["ghat"]), _p(ws["Mk"]), _p(ws["Bk"]), _p(ws["cones"]), _p(ws["cstatus"]), _p(ws["y"]),
-            _p(ws["status"]), _p(ws["iters"]), dt, L_true, Bt, N, Kob, max_iters, 1 if shared else 0)
+    tail = ()                                              # the sampled entry: (kernel_kind, z, xdot_s, cbc_s)
+    if sampled is not None:
+        z, xdot_s, cbc_s = sampled["z"], sampled.get("xdot_s"), sampled.get("cbc_s")
+        _chk(x, z, xdot_s, cbc_s)
+        if z is None or tuple(z.shape) != (Bt, 3):
+            raise ValueError("sampled['z'] must be a [Bt,3] tensor of standard-normal draws")
+        if (xdot_s is not None and tuple(xdot_s.shape) != (Bt, 3)) or (cbc_s is not None and tuple(cbc_s.shape) != (Bt, 1 + Kob)):
+            raise ValueError("sampled['xdot_s'] is [Bt,3] and sampled['cbc_s'] is [Bt,1+Kob]")
+        tail = (DATA_KERNELS.index(kernel), _p(z), _p(xdot_s), _p(cbc_s))
+        keep += (dict(sampled),)
     obs_cfg = observe or {}
     xq, xq_next = obs_cfg.get("xq"), obs_cfg.get("xq_next")
     _chk(x, xq, xq_next)
     p_xq, p_next = _p(xq), _p(xq_next)
     flags = (1 if obs_cfg.get("shift_invariant", True) else 0) | (2 if obs_cfg.get("advance_plan", False) else 0)
-    tail = (DATA_KERNELS.index(kernel), _p(z), _p(xdot_s), _p(cbc_s))
-    keep = (dict(gp), dict(task), dict(ws), x, A, stream, observe, dict(sampled))
-    dev, y = x.device, ws["y"]
-    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
 
     def step(ev_start=None, ev_stop=None, obs=None):
-        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
-        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
         o = (None, None, None, 1) if obs is None else (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
-        rc = fn(*head, p_xq, *o, p_next, flags, *tail, ev0, ev1,
-                fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc:
-            check(rc, "bcbf_unicycle_control_step_sampled")
-        return y
+        return call(ev_start, ev_stop, (*head, p_xq, *o, p_next, flags, *tail))
     step.keep = keep
     return step
 
@@ -1876,21 +1844,15 @@ def pendulum_control_step_prepare(gp, ws, x, mean_model=None, true_model=(1.0, 1
             float(relax_weight), HESSIAN_MODES[hessian_mode], int(max_iters), float(true_model[0]), float(true_model[1]),
             float(true_model[2]), float(dt), _p(x)) + tuple(
         _p(ws[k]) for k in ("Mk", "Bk", "G", "Mj", "h", "gh", "Hh", "u_ref", "terms2", "terms", "tstatus", "Gc", "hc",
-                            "cstatus", "P", "q", "y", "sstatus", "iters", "u", "status")) + (_p(min_h), _p(fails), Bt, 2, 1)
+                            "cstatus", "P", "q", "y", "sstatus", "iters", "u", "status")) + (_p(min_h), _p(fails))
     keep = (gp, dict(ws), x, kalpha, xg, Qg, u_ref, stats, stream)      # the pointers above live as long as these
-    dev, out = x.device, ws["u"]
-    fixed = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     if learn:
-        return _pendulum_observe_step(head[:-3], keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled, nom)
-    fn = lib.bcbf_pendulum_control_step_f64
+        return _pendulum_observe_step(head, keep, x, ws["u"], stream, prior, explore, eps, ctrl_range, u_ref, sampled, nom)
+    call = _bind_call(lib.bcbf_pendulum_control_step_f64, "bcbf_pendulum_control_step", x, stream, ws["u"])
+    args = head + (Bt, 2, 1)
 
     def step(ev_start=None, ev_stop=None):
-        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
-        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
-        rc = fn(*head, ev0, ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc:
-            check(rc, "bcbf_pendulum_control_step")
-        return out
+        return call(ev_start, ev_stop, args)
     step.keep = keep
     return step
 
@@ -1913,37 +1875,31 @@ def _pendulum_sampled_args(x, sampled):
     return (_p(z), _p(xdot_s), _p(cbc_s), _p(relaxed), _p(viol_relaxed), float(sampled.get("rho_tol", 1e-6)))
 
 
-def _pendulum_observe_step(head, keep, x, out, fixed, prior, explore, eps, ctrl_range, u_ref, sampled=None, nom=None):
-    """The step of `pendulum_control_step_prepare` on bcbf_pendulum_control_step_observe_f64 (head: the plain entry's
-    arguments up to `fails`), or with `sampled` on bcbf_pendulum_control_step_sampled_f64, or with `nom` (the LQR nominal
+def _pendulum_observe_step(head, keep, x, out, stream, prior, explore, eps, ctrl_range, u_ref, sampled=None, nom=None):
+    """The step of `pendulum_control_step_prepare` on bcbf_pendulum_control_step_observe_f64 (head: the arguments every entry
+    takes, up to `fails`), or with `sampled` on bcbf_pendulum_control_step_sampled_f64, or with `nom` (the LQR nominal
     controller's numSteps, t, t_dev, lstatus) on bcbf_pendulum_control_step_nominal_f64."""
     if explore is not None and u_ref is not None:
         raise ValueError("explore wraps the greedy u_ref; it cannot be combined with a caller's u_ref")
     _chk(x, explore)
     rng = None if ctrl_range is None else (ctypes.c_double * 2)(*[float(v) for v in ctrl_range])
-    fn, dev, Bt = lib.bcbf_pendulum_control_step_observe_f64, x.device, x.shape[0]
-    what, draw = "bcbf_pendulum_control_step_observe", ()
+    Bt, what, draw = x.shape[0], "bcbf_pendulum_control_step_observe", ()
     if sampled is not None:
-        fn, what, draw = lib.bcbf_pendulum_control_step_sampled_f64, "bcbf_pendulum_control_step_sampled", _pendulum_sampled_args(x, sampled)
+        what, draw = "bcbf_pendulum_control_step_sampled", _pendulum_sampled_args(x, sampled)
     if nom is not None:
-        fn, what = lib.bcbf_pendulum_control_step_nominal_f64, "bcbf_pendulum_control_step_nominal"
-        draw = draw or (None, None, None, None, None, 1e-6)
+        what, draw = "bcbf_pendulum_control_step_nominal", draw or (None, None, None, None, None, 1e-6)
+    call = _bind_call(getattr(lib, what + "_f64"), what, x, stream, out)
     bound = dict(eps=float(eps), explore=explore)
     keep = keep + (rng, explore, None if sampled is None else dict(sampled), nom)
 
     def step(ev_start=None, ev_stop=None, eps=None, explore=None, obs=None, t=None):
-        ev0 = ctypes.c_void_p(ev_start.cuda_event) if ev_start is not None else None
-        ev1 = ctypes.c_void_p(ev_stop.cuda_event) if ev_stop is not None else None
         ex = bound["explore"] if explore is None else explore
         if explore is not None:
             _chk(x, explore)
         o = (None, None, None, 1) if obs is None else (_p(obs[0]), _p(obs[1]), _p(obs[2]), int(obs[3]))
         lq = () if nom is None else (nom["code"], nom["numSteps"], nom["t"] if t is None else int(t), _p(nom["t_dev"]), _p(nom["lstatus"]))
-        rc = fn(*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, *draw, *lq, Bt, 2, 1, ev0,
-                ev1, fixed if fixed is not None else ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc:
-            check(rc, what)
-        return out
+        return call(ev_start, ev_stop, (*head, 1 if prior else 0, _p(ex), float(bound["eps"] if eps is None else eps), rng, *o, *draw,
+                                        *lq, Bt, 2, 1))
     step.keep = keep
     step.lstatus = None if nom is None else nom["lstatus"]
     return step

@@ -107,6 +107,29 @@ int main(void) {
                                                   0.01, 1.0, 1, 0, 2, 20, 0, 0, d, 0, d, 1, 0, 1, 0, 0, 0), BCBF_EINVAL);   /* observation outputs: all three or none */
     EXPECT(bcbf_unicycle_control_step_observe_f64(0, 0, 0, 0, 0, 0, 0, 0, d, d, d, d, d, 10.0, d, d, d, d, 1.0, d, d, d, d, d, d, d, d, d, d, d, d, i, d, i, i,
                                                   0.0, 1.0, 1, 0, 2, 20, 0, 0, d, d, d, 1, 0, 1, 0, 0, 0), BCBF_EINVAL);    /* an observation needs dt > 0 */
+    /* the sampled control step: the observing entry's arguments, then (kernel_kind, z, xdot_s, cbc_s) */
+    EXPECT(bcbf_unicycle_control_step_sampled_f64(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 10.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+                                                  0.01, 1.0, 0, 8, 2, 20, 0, 0, 0, 0, 0, 1, 0, 3, 0, 0, 0, 0, 0, 0, 0), BCBF_OK);
+    EXPECT(bcbf_unicycle_control_step_sampled_f64(0, 0, 0, 0, 0, 0, 0, 0, d, d, d, d, d, 10.0, d, d, d, d, 1.0, d, d, d, d, d, d, d, d, d, d, d, d, i, d, i, i,
+                                                  0.01, 1.0, 1, 0, 2, 20, 0, 0, 0, 0, 0, 1, 0, 1, 0, 0, d, d, 0, 0, 0), BCBF_EINVAL);   /* z == NULL */
+    EXPECT(bcbf_unicycle_control_step_sampled_f64(0, 0, 0, 0, 0, 0, 0, 0, d, d, d, d, d, 10.0, d, d, d, d, 1.0, d, d, d, d, d, d, d, d, d, d, d, d, i, d, i, i,
+                                                  0.01, 1.0, 1, 0, 2, 20, 0, 0, 0, 0, 0, 1, 0, 1, 3, d, d, d, 0, 0, 0), BCBF_EINVAL);   /* unknown kernel kind */
+    /* the pendulum's control steps: every check runs before the empty batch returns.  The 56 arguments the four entries share
+     * (dt, x: what the refusals below vary), then each entry's groups, then (Bt, n, m, ev_start, ev_stop, stream) */
+#define PEND_HEAD(dt, x) d, d, d, d, d, d, d, d, d, 16, 0, 0, 1, 1.0, 10.0, 1.0, 0.785, 0.393, d, d, d, 1.0, 0, 9.95, 1.0, 100.0, 0, 100, \
+                         1.0, 10.0, 1.0, (dt), (x), d, d, d, d, d, d, d, d, d, d, i, d, d, i, d, d, d, i, i, d, i, d, i
+#define PEND_LEARN(obs_ld) 0, 0, 0.0, 0, d, d, d, (obs_ld)
+    EXPECT(bcbf_pendulum_control_step_f64(PEND_HEAD(0.002, d), 0, 2, 1, 0, 0, 0), BCBF_OK);
+    EXPECT(bcbf_pendulum_control_step_f64(PEND_HEAD(0.0, d), 0, 2, 1, 0, 0, 0), BCBF_EINVAL);                       /* dt == 0 */
+    EXPECT(bcbf_pendulum_control_step_observe_f64(PEND_HEAD(0.002, d), PEND_LEARN(250), 0, 2, 1, 0, 0, 0), BCBF_OK);
+    EXPECT(bcbf_pendulum_control_step_observe_f64(PEND_HEAD(0.002, d), PEND_LEARN(0), 0, 2, 1, 0, 0, 0), BCBF_EINVAL);   /* obs_ld < 1 */
+    EXPECT(bcbf_pendulum_control_step_sampled_f64(PEND_HEAD(0.002, d), PEND_LEARN(1), d, d, d, i, i, 1e-6, 0, 2, 1, 0, 0, 0), BCBF_OK);
+    EXPECT(bcbf_pendulum_control_step_sampled_f64(PEND_HEAD(0.002, d), PEND_LEARN(1), 0, d, d, i, i, 1e-6, 0, 2, 1, 0, 0, 0), BCBF_EINVAL);   /* z == NULL */
+    EXPECT(bcbf_pendulum_control_step_sampled_f64(PEND_HEAD(0.002, 0), PEND_LEARN(1), d, d, d, i, i, 1e-6, 0, 2, 1, 0, 0, 0), BCBF_EINVAL);   /* x == NULL */
+    EXPECT(bcbf_pendulum_control_step_nominal_f64(PEND_HEAD(0.002, d), PEND_LEARN(1), d, d, d, i, i, 1e-6, 1, 250, 0, 0, i, 0, 2, 1, 0, 0, 0), BCBF_OK);
+    EXPECT(bcbf_pendulum_control_step_nominal_f64(PEND_HEAD(0.002, d), PEND_LEARN(1), 0, 0, 0, 0, 0, 1e-6, 0, 0, -1, 0, 0, 0, 2, 1, 0, 0, 0), BCBF_OK);   /* greedy, no draws */
+    EXPECT(bcbf_pendulum_control_step_nominal_f64(PEND_HEAD(0.002, d), PEND_LEARN(1), d, d, d, i, i, 1e-6, 2, 250, 0, 0, i, 0, 2, 1, 0, 0, 0), BCBF_EINVAL);   /* nominal: 0 or 1 */
+    EXPECT(bcbf_pendulum_control_step_nominal_f64(PEND_HEAD(0.002, d), PEND_LEARN(1), d, d, d, i, i, 1e-6, 1, 250, 0, 0, 0, 0, 2, 1, 0, 0, 0), BCBF_EINVAL);   /* the LQR needs lstatus */
     {   /* the row-count helper is pure host logic */
         int kinds[4] = {1, 2, 0, 1};
         EXPECT(bcbf_controller_cones_rows(kinds, 4, 2, 1) == 1 + 4 + 3 * 4 ? 0 : 1, 0);

@@ -136,6 +136,45 @@ def test_observation_rows_are_the_facades_training_set_bit_for_bit(shift_invaria
         assert torch.equal(Yd, Ydiv - mean), float((Yd - (Ydiv - mean)).abs().max())
 
 
+@pytest.mark.parametrize("model", ["per-instance", "shared"])
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["fp64", "fp32"])
+def test_observing_step_with_nothing_to_observe_is_the_plain_step_bit_for_bit(dtype, model):
+    """`unicycle_control_step_prepare(observe=dict(xq=None, xq_next=None))` called with no `obs` == the plain step, bit for bit:
+    both entries run the same posterior launch at x and the same instantiation of the solve / plant kernel (it is chosen by the
+    draws `z` alone; an observation is a run-time NULL test).  Bt = 5 (no multiple of a quad or a wave), N = 40 (padded to 64, a
+    partial block), Kob = 2, dt = 0.01, three steps; one model per instance, and one shared model (leading axis 1)."""
+    from bayesian_cbf_amd import ops
+    from bayesian_cbf_amd.synthetic import make_instances, make_unicycle_task
+    Bt, N, Kob, dt, steps = 5, 40, 2, 0.01, 3
+    p = make_instances(Bt if model == "per-instance" else 1, N, 3, 2, dtype=dtype, device=DEV, seed=81)
+    task = make_unicycle_task(Bt, dtype=dtype, device=DEV, seed=82)
+    assert task["centers"].shape[1] == Kob
+    jit = p["jitter"]
+    for _ in range(4):                                       # make_psd's x10 retry, as the benchmark refits
+        Lop, UHB, info, _ = ops.refit(p["X"], p["UH"], p["Bm"], p["ell"], p["s2"], jit)
+        if not bool((info != 0).any()):
+            break
+        jit = torch.where((info != 0)[:, None], jit * 10, jit).contiguous()
+    assert int((info != 0).sum()) == 0
+    Vw, _ = ops.potrs(Lop, p["Xdot"], p["UH"], p["M0"], want_alpha=False)
+    gp = dict(Lop=Lop, Vw=Vw, X=p["X"], UHB=UHB, ell=p["ell"], s2=p["s2"], Bm=p["Bm"], M0=p["M0"], A=(0.01 * p["A"]).contiguous())
+    runs = []
+    for observe in (None, dict(xq=None, xq_next=None)):
+        x, ws = task["x"].clone(), ops.control_workspace(Bt, Kob, dtype, DEV)
+        for v in ws.values():
+            v.fill_(7)                                       # a buffer one of the two entries leaves unwritten shows
+        step = ops.unicycle_control_step_prepare(gp, task, ws, x, dt=dt, L_true=12.0, L_mean=4.0, clf_gamma=10.0, max_iters=40,
+                                                 observe=observe)
+        for _ in range(steps):
+            step()
+        torch.cuda.synchronize()
+        runs.append(dict(ws, x=x))
+    plain, observing = runs
+    assert not torch.equal(plain["x"], task["x"]) and int((plain["status"] == 0).sum()) >= 1      # the batch moved
+    for k in ("x", "y", "status", "iters", "Mk", "Bk", "cones", "cstatus", "grad", "cst", "fhat", "ghat"):
+        assert torch.equal(plain[k], observing[k]), k
+
+
 def test_refit_retry_factors_only_the_failed_instances():
     """bcbf_refit_retry: instances whose previous info is 0 are not touched (their operator stays bit for bit), the failed ones are
     factored with the raised jitter and equal a direct refit at that jitter; info reports 0 for both; the fp32 one-wave form, the
