@@ -145,6 +145,9 @@ _TSIGS = {
     "bcbf_obstacle_field_select": [P, P, P, c_int, P] + [P] * 6 + [c_int] * 3 + [P],
     "bcbf_obstacle_field_audit": [P] * 11 + [c_int, P, "T", c_double, c_double] + [P] * 8 + [c_int] * 3 + [P],
     "bcbf_obstacle_field_commit": [P] * 5 + ["T", "T", c_int, P],
+    # the commit on a posterior-drawn plant: (x .. radii_f, field_stride, tw, gamma, idx, z, status_eff, the 6 outputs of the step,
+    # the 6 accumulators, dt, Bt, Kf, S, stream)
+    "bcbf_obstacle_field_commit_sampled": [P] * 12 + [c_int, P, "T"] + [P] * 15 + ["T"] + [c_int] * 3 + [P],
     "bcbf_rollout_stats": [P] * 8 + [c_int, c_int, c_int, P],
     "bcbf_unicycle_control_step": _UNI_HEAD + _STREAM,
     "bcbf_unicycle_control_step_matern52": _UNI_HEAD + _STREAM,

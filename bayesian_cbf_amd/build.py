@@ -21,7 +21,7 @@ OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libbcbf.so")
 ARCH = "gfx950"
 SOURCES = ["common.hip", "posterior_step.hip", "jets_mfma.hip", "posterior_shared.hip", "posterior_shared_reg.hip", "refit.hip", "refit_mfma.hip", "refit_mfma64.hip", "refit_wave64.hip", "solve.hip", "trtri.hip", "tail.hip", "syrk.hip", "mll_grad.hip", "fit.hip", "cbc_terms.hip", "predict_assemble.hip", "gram.hip", "controller_cones.hip", "socp.hip", "socp_quad.hip",
-           "unicycle.hip", "control_step.hip", "subsample.hip", "pendulum.hip", "trigger.hip", "trigger_step.hip", "pendulum_qp.hip", "lqr.hip", "unicycle_qp.hip", "obstacle_field.hip"]
+           "unicycle.hip", "control_step.hip", "subsample.hip", "pendulum.hip", "trigger.hip", "trigger_step.hip", "pendulum_qp.hip", "lqr.hip", "unicycle_qp.hip", "obstacle_field.hip", "field_plant.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
          "-I" + CSRC, "-Wall", "-Wno-unused-function", "-fvisibility=hidden"]
 # per-file extras.  posterior_shared: MFMA results are consumed by VALU code every block, so keep the accumulators
@@ -35,7 +35,8 @@ EXTRA_FLAGS = {"posterior_shared.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "pendulum_qp.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "unicycle_qp.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "pendulum.hip": ["-Rpass-analysis=kernel-resource-usage"],
-               "obstacle_field.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+               "obstacle_field.hip": ["-Rpass-analysis=kernel-resource-usage"],
+               "field_plant.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 # instantiations of the streaming kernel whose measured figures assume ZERO scratch (a spill in the streaming loop is fatal
 # there: DESIGN.md 3.1 -- 1373 us against 470): the headline (fp32 / fp64 values-only, C = 2..3), the fp32 jets of the pendulum and
 # unicycle shapes, the fp32 fused query + append column.  Demangled-name prefixes; the build fails when one of them reports scratch
@@ -55,7 +56,9 @@ ZERO_SCRATCH_KERNELS = {"posterior_step.hip": [
     # the posterior-drawn plant: two Cholesky factors, the draw and the condition live in registers (every index a constant)
     "pendulum.hip": ["pendulum_sampled_plant_kernel<double>"],
     # the obstacle-field working set: per-lane keys and slot margins in register arrays indexed by constants only
-    "obstacle_field.hip": ["obstacle_field_%s_kernel<%s>" % (k, t) for k in ("select", "audit", "commit") for t in ("float", "double")]}
+    "obstacle_field.hip": ["obstacle_field_%s_kernel<%s>" % (k, t) for k in ("select", "audit", "commit") for t in ("float", "double")],
+    # the field's commit on a posterior-drawn plant: the audit's mapping, running minima instead of per-lap arrays
+    "field_plant.hip": ["field_plant_kernel<float>", "field_plant_kernel<double>"]}
 # kernels that must not touch scratch memory (posterior_shared_reg: an operand spilled between its explicit LDS read and
 # the explicit wait for it would be stored before it has arrived).  Their device assembly is also linted: no instruction may
 # name the destination of an LDS read that has not been waited for (check_lds_waits.py)

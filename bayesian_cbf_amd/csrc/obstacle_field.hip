@@ -9,34 +9,10 @@
 //   commit  one lane per instance: the effective status, and the plant step of the certified instances
 // Arithmetic is fp64 for both entry precisions (inputs read as stored): the decisions do not depend on the entry's dtype.
 // No LDS, no scratch (every register array is indexed by compile-time constants; the build's resource guard checks it).
-#include <limits>
-#include <stdio.h>
-#include "bcbf_common.h"
-#include "unicycle_task.h"
+// (The commit on a plant drawn from the posterior is field_plant.hip; what both files share is obstacle_field.h.)
+#include "obstacle_field.h"
 
 namespace bcbf {
-
-constexpr int FIELD_LAPS = BCBF_MAX_FIELD / 64;      // discs per lane
-constexpr int FIELD_WAVES = 4;                       // instances per workgroup (waves never talk to each other)
-
-// (value, index) pairs, ordered by value then by index: the wave's minimum, known to every lane afterwards
-__device__ inline void wave_lexmin(double& v, int& i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(v, off, 64);
-        const int oi = __shfl_xor(i, off, 64);
-        if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-}
-
-// ObstacleCBF of one disc at (px, py, th) in fp64: grad h, and gam * h  (unicycle_row's obstacle branch)
-__device__ inline void field_row(double px, double py, double th, double cx, double cy, double rad, double tw0, double tw1,
-                                 double gam, double (&g)[3], double& cst) {
-    const double z[3] = {0.0, 0.0, 0.0};
-    unicycle_row_vals<double>(1, px, py, th, z, z, z, 0.0, cx, cy, rad, tw0, tw1, gam, g, cst);
-}
-
-constexpr int FIELD_NONE = 0x7fffffff;               // "no disc": above every index
 
 template <typename T>
 __global__ __launch_bounds__(64 * FIELD_WAVES) void obstacle_field_select_kernel(
@@ -228,23 +204,6 @@ __global__ void obstacle_field_commit_kernel(T* __restrict__ x, const T* __restr
                            y[(size_t)b * 3 + 1], dt, L_true, n0, n1, n2);
         x[(size_t)b * 3] = n0; x[(size_t)b * 3 + 1] = n1; x[(size_t)b * 3 + 2] = n2;
     }
-}
-
-static int field_einval(const char* entry, const char* why) {
-    char msg[240];
-    snprintf(msg, sizeof(msg), "%s: %s", entry, why);
-    set_error_message(msg);
-    return BCBF_EINVAL;
-}
-
-static bool field_finite(double v) { return fabs(v) <= std::numeric_limits<double>::max(); }
-
-static const char* field_shape(int Bt, int Kf, int S, int field_stride) {
-    if (Bt <= 0) return "Bt <= 0";
-    if (S < 1 || S > 3) return "S must be 1..3 (the fused solver's obstacle lanes)";
-    if (Kf < S || Kf > BCBF_MAX_FIELD) return "Kf must be S..BCBF_MAX_FIELD";
-    if (field_stride != 0 && field_stride != 1) return "field_stride must be 0 (shared) or 1 (per instance)";
-    return nullptr;
 }
 
 template <typename T>

@@ -1460,8 +1460,51 @@ def obstacle_field_commit(x, y, status, fws, dt=0.0, L_true=1.0):
     return fws["status_eff"]
 
 
+_FIELD_RISK_STEP = ("xdot_s", "cbc_min", "cbc_argmin", "tight_idx", "cbc_tight", "nneg")
+_FIELD_RISK_SUMS = ("solved", "viol_tight", "viol_any", "viol_unselected", "viol_discs", "min_cbc")
+
+
+def obstacle_field_risk_workspace(Bt, dtype, device):
+    """Buffers of `obstacle_field_commit_sampled`: the caller's normals z[Bt,3]; the outputs of one step -- xdot_s[Bt,3], cbc_min,
+    cbc_tight [Bt], cbc_argmin, tight_idx, nneg [Bt] int32; and the accumulators -- solved, viol_tight, viol_any, viol_unselected,
+    viol_discs [Bt] int32 = 0, min_cbc[Bt] = +inf."""
+    f = dict(dtype=dtype, device=device)
+    i = dict(dtype=torch.int32, device=device)
+    ws = dict(z=torch.zeros(Bt, 3, **f), xdot_s=torch.zeros(Bt, 3, **f), cbc_min=torch.zeros(Bt, **f), cbc_tight=torch.zeros(Bt, **f),
+              min_cbc=torch.full((Bt,), float("inf"), **f))
+    ws.update({k: torch.zeros(Bt, **i) for k in ("cbc_argmin", "tight_idx", "nneg") + _FIELD_RISK_SUMS[:5]})
+    return ws
+
+
+def obstacle_field_commit_sampled(x, ws, A, rho, field, tw, gamma, fws, risk, dt=0.0):
+    """bcbf_obstacle_field_commit_sampled, in place of `obstacle_field_commit` on a plant DRAWN FROM THE MODEL'S POSTERIOR: writes
+    status_eff as the plain commit does; an instance with status_eff = 0 advances by one draw xdot_s = fhat + ghat u + M_k ubar +
+    sqrt(ubar' B_k ubar) chol(A) z (risk['z']: the caller's standard normals, refilled before every step), and the condition of
+    EVERY disc of the field is evaluated on that draw at the state before the step: cbc_min / cbc_argmin, the tightest cone (smallest
+    audit margin) tight_idx and its drawn condition cbc_tight, nneg = the number of negative conditions, and the accumulators of
+    `obstacle_field_risk_workspace`.  Every other instance keeps its state and its accumulators.  dt = 0: the state stays."""
+    cen, rad, stride, Kf = _field_args(x, field)
+    _chk(x, ws["y"], ws["status"], ws["Mk"], ws["Bk"], A, ws["fhat"], ws["ghat"], rho, tw, fws["idx"], fws["cert"], fws["status_eff"],
+         *(risk[k] for k in ("z",) + _FIELD_RISK_STEP + _FIELD_RISK_SUMS))
+    Bt, S = fws["idx"].shape
+    if A.shape[0] != Bt:
+        raise ValueError("A must be [Bt,3,3] (one kernel matrix per instance, as the fused step reads it)")
+    if tuple(risk["z"].shape) != (Bt, 3) or risk["z"].dtype != x.dtype:
+        raise ValueError("risk['z'] must be a [Bt,3] tensor of standard-normal draws in x's dtype")
+    for k in _FIELD_RISK_STEP + _FIELD_RISK_SUMS:
+        want = x.dtype if k in ("xdot_s", "cbc_min", "cbc_tight", "min_cbc") else torch.int32
+        if risk[k].dtype != want or tuple(risk[k].shape) != ((Bt, 3) if k == "xdot_s" else (Bt,)):
+            raise ValueError("risk[%r]: the buffers of obstacle_field_risk_workspace(Bt, x.dtype, x.device)" % k)
+    check(getattr(lib, "bcbf_obstacle_field_commit_sampled" + _suf(x))(
+        _p(x), _p(ws["y"]), _p(ws["status"]), _p(fws["cert"]), _p(ws["Mk"]), _p(ws["Bk"]), _p(A), _p(ws["fhat"]), _p(ws["ghat"]),
+        _p(rho), _p(cen), _p(rad), stride, _p(tw), float(gamma), _p(fws["idx"]), _p(risk["z"]), _p(fws["status_eff"]),
+        *(_p(risk[k]) for k in _FIELD_RISK_STEP + _FIELD_RISK_SUMS), float(dt), Bt, Kf, S, _stream(x)),
+        "bcbf_obstacle_field_commit_sampled")
+    return fws["status_eff"]
+
+
 def unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=3, dt=0.0, L_true=1.0, L_mean=1.0, clf_gamma=10.0,
-                                        max_iters=100, fws=None, tol_f=None, tol_a=None, stats=True):
+                                        max_iters=100, fws=None, tol_f=None, tol_a=None, stats=True, sampled=None):
     """The chance-constrained control step among the Kf <= 256 discs of `field` = dict(centers[Bf,Kf,2], radii[Bf,Kf]) (Bf = 1: one
     field for all instances).  Returns step(): on the current stream, with no host look at the device (capturable),
         select -> the fused control step on the working set (dt = 0) -> audit
@@ -1472,7 +1515,11 @@ def unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=3, dt=0.0
     its 'centers' / 'radii' are replaced by the working set's.  ws = control_workspace(Bt, S); fws = obstacle_field_workspace(Bt, S)
     (made here when None): step.fws.  status_eff[b] = 0 where the step is the certified optimum of the FULL program and the plant
     moved (dt > 0); BCBF_FIELD_UNCERTIFIED (6) where `rounds` did not suffice or the working set is full; the solver's status
-    where the working-set program was not solved.  The observing, sampled and self-triggered steps are out of scope."""
+    where the working-set program was not solved.
+    sampled = dict(z=[Bt,3], risk=obstacle_field_risk_workspace(Bt, ...)): the plant is DRAWN FROM THE MODEL'S POSTERIOR -- the
+    commit is `obstacle_field_commit_sampled` (L_true is ignored), reading the caller's normals from `z` (refill it in place before
+    every step; risk['z'] when `z` is absent) and counting the drawn conditions of every disc into `risk`.  Still capturable.
+    sampled = None enqueues exactly the true-plant step.  The observing and self-triggered steps are out of scope."""
     if rounds < 1:
         raise ValueError("rounds must be >= 1")
     Bt = x.shape[0]
@@ -1496,6 +1543,11 @@ def unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=3, dt=0.0
         again = unicycle_control_step_prepare(dict(A=gp["A"]), task, ws, x, 0.0, L_true, L_mean, clf_gamma, max_iters)
     _, A, _, _ = _control_step_args(gp, task, ws, x)
     tw, rho, w = task["tw"], task["rho"], task["w"]
+    risk = None
+    if sampled is not None:
+        risk = dict(sampled["risk"])
+        if sampled.get("z") is not None:
+            risk["z"] = sampled["z"]
 
     def step():
         obstacle_field_select(x, field, tw, fws)
@@ -1504,12 +1556,15 @@ def unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=3, dt=0.0
         for _ in range(rounds - 1):
             again()
             obstacle_field_audit(x, ws, A, rho, field, tw, gamma, fws, tol_f, tol_a)
-        obstacle_field_commit(x, ws["y"], ws["status"], fws, dt, L_true)
+        if risk is None:
+            obstacle_field_commit(x, ws["y"], ws["status"], fws, dt, L_true)
+        else:
+            obstacle_field_commit_sampled(x, ws, A, rho, field, tw, gamma, fws, risk, dt)
         if stats:
             rollout_stats(ws["cst"], ws["y"], fws["status_eff"], w, gam, fws["min_h"], fws["cost"], fws["fails"])
         return ws["y"]
     step.fws = fws
-    step.keep = (first, again, task, field, A)
+    step.keep = (first, again, task, field, A, risk)
     return step
 
 

@@ -185,7 +185,7 @@ def random_obstacle_field(Kf, start=(-3.0, -1.0, -math.pi / 4), goal=(0.0, 0.0, 
 def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_diag_A=(1e-2, 1e-2, 1e-2), L_mean=1.0, L_true=12.0,
                             start=(-3.0, -1.0, -math.pi / 4), goal=(0.0, 0.0, math.pi / 4), start_noise=0.05, max_risk=0.01,
                             dtype=torch.float64, device="cuda", seed=0, slots=3, rounds=3, record=False, max_iters=30,
-                            use_graph=False, tol_f=None, tol_a=None):
+                            use_graph=False, tol_f=None, tol_a=None, plant="true", x_start=None, z_all=None):
     """`monte_carlo_safety_rollouts` among the discs of `field` = dict(centers[Kf,2] or [Bt,Kf,2], radii) -- up to 256 of them
     (`random_obstacle_field`): every step solves the program on a working set of `slots` discs and certifies it against the whole
     field (`ops.unicycle_field_control_step_prepare`, at most `rounds` solves).  A step that is not certified, or not solved, is
@@ -193,7 +193,21 @@ def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_di
     The result of `monte_carlo_safety_rollouts` (min_h over the WHOLE field), plus over all instance-steps:
     certified_steps, rounds_hist[rounds] (certified after r swaps), uncertified_steps (rounds ran out), full_set_steps (every slot
     active and a disc still violated), unsolved_steps (the working-set program was not solved); with record, traj[numSteps+1,Bt,3],
-    y[numSteps,Bt,3], cert, rounds_rec, status_eff [numSteps,Bt] and idx[numSteps,Bt,slots]."""
+    y[numSteps,Bt,3], cert, rounds_rec, status_eff [numSteps,Bt] and idx[numSteps,Bt,slots].
+    plant: "true" (default) -- the Ackermann drive with L_true -- or "posterior": every certified step is taken on a draw from the
+    model's own posterior (`ops.obstacle_field_commit_sampled`; L_true is ignored) and the condition of EVERY disc of the field is
+    evaluated on that draw.  The normals z_all[numSteps,Bt,3] are drawn once from the seeded device generator, after the start
+    noise, and row t is gathered like the plan row: the same bits eager and under use_graph.  The result gains
+    risk = dict(tight, joint, unselected -- rates over the solved (certified) instance-steps: the drawn condition of the tightest
+    cone was negative (what max_risk promises, per cone), ANY disc's was (which only the union bound covers), a disc's outside the
+    working set was; mean_discs_violated, min_cbc, instance_steps, max_risk) (`distributed.reduce_risk_stats`), solved[Bt] and the
+    per-instance counters risk_counters; with record also cbc_min, cbc_tight, cbc_argmin, tight_idx, nneg [numSteps,Bt].  Draws of
+    different steps are independent (exact per-step marginals, not one function drawn along the trajectory).
+    x_start[Bt,3] / z_all[numSteps,Bt,3]: the caller's start states / normals in place of the seeded ones (a study that pairs or
+    permutes instances)."""
+    if plant not in ("true", "posterior"):
+        raise ValueError("plant must be 'true' or 'posterior', got %r" % (plant,))
+    sampled = plant == "posterior"
     dev = torch.device(device)
     f = dict(dtype=dtype, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
@@ -207,6 +221,8 @@ def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_di
     field = dict(centers=field["centers"].to(**f).contiguous(), radii=field["radii"].to(**f).contiguous())
     planner = PiecewiseLinearPlanner(x0, xg, numSteps, dt, frac_time_to_reach_goal=0.95)
     x = (x0 + start_noise * torch.randn(Bt, 3, generator=gen, **f)).contiguous()
+    if x_start is not None:
+        x = x_start.to(**f).reshape(Bt, 3).clone().contiguous()
     ws = ops.control_workspace(Bt, S, dtype, dev)
     fws = ops.obstacle_field_workspace(Bt, S, dtype, dev)
     if gp is None:
@@ -221,22 +237,34 @@ def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_di
     counts = torch.zeros(rounds + 3, dtype=torch.long, device=dev)
     bin_ids = torch.arange(rounds + 3, **i32)
     state =[x, fws["min_h"], fws["cost"], fws["fails"], counts]
+    risk = draw = None
+    if sampled:
+        z_all = torch.randn(numSteps, Bt, 3, generator=gen, **f) if z_all is None else z_all.to(**f).reshape(numSteps, Bt, 3).contiguous()
+        risk = ops.obstacle_field_risk_workspace(Bt, dtype, dev)
+        draw = dict(z=risk["z"], risk=risk)
+        state += [risk[k] for k in ops._FIELD_RISK_SUMS]
     step = ops.unicycle_field_control_step_prepare(gp, task, field, ws, x, rounds=rounds, dt=dt, L_true=L_true, L_mean=L_mean,
-                                                   max_iters=max_iters, fws=fws, tol_f=tol_f, tol_a=tol_a)
+                                                   max_iters=max_iters, fws=fws, tol_f=tol_f, tol_a=tol_a, sampled=draw)
     rec = None
     if record:
         rec = dict(traj=torch.empty(numSteps + 1, Bt, 3, **f), y=torch.empty(numSteps, Bt, 3, **f),
                    cert=torch.empty(numSteps, Bt, **i32), rounds_rec=torch.empty(numSteps, Bt, **i32),
                    status_eff=torch.empty(numSteps, Bt, **i32), idx=torch.empty(numSteps, Bt, S, **i32))
         rec["traj"][0] = x
+        if sampled:
+            rec.update({k: torch.empty(numSteps, Bt, dtype=risk[k].dtype, device=dev) for k in ops._FIELD_RISK_STEP[1:]})
 
     def one_step(t):
         if torch.is_tensor(t):
             task["plan"].copy_(plan_all.index_select(0, t))
             task["dot_plan"].copy_(dplan_all.index_select(0, t))
+            if sampled:
+                risk["z"].copy_(z_all.index_select(0, t)[0])
         else:
             task["plan"].copy_(plan_all[t])
             task["dot_plan"].copy_(dplan_all[t])
+            if sampled:
+                risk["z"].copy_(z_all[t])
         step()
         cert, eff = fws["cert"], fws["status_eff"]
         # bin per instance: certified -> its number of swaps; else rounds (uncertified), rounds + 1 (full), rounds + 2 (unsolved)
@@ -275,6 +303,9 @@ def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_di
             rec["y"][t] = ws["y"]
             rec["cert"][t], rec["rounds_rec"][t], rec["status_eff"][t] = fws["cert"], fws["rounds"], fws["status_eff"]
             rec["idx"][t] = fws["idx"]
+            if sampled:
+                for k in ops._FIELD_RISK_STEP[1:]:
+                    rec[k][t] = risk[k]
     torch.cuda.synchronize(dev)
     t_loop = time.perf_counter() - t_loop
     min_h, cost, fails = fws["min_h"], fws["cost"], fws["fails"]
@@ -284,6 +315,15 @@ def obstacle_field_rollouts(Bt, field, numSteps=200, dt=0.05, gp=None, kernel_di
     out = dict(stats=stats, x_final=x, min_h=min_h, dist_to_goal=(x[:, :2] - xg[:2]).norm(dim=1), loop_seconds=t_loop,
                certified_steps=sum(c[:rounds]), rounds_hist=c[:rounds], uncertified_steps=c[rounds], full_set_steps=c[rounds + 1],
                unsolved_steps=c[rounds + 2], traj=None)
+    if sampled:
+        sums = torch.stack([risk[k].sum() for k in ("viol_tight", "viol_any", "viol_unselected", "viol_discs")])
+        r = reduce_risk_stats(risk["solved"].sum(), sums, risk["min_cbc"].min().reshape(1), max_risk)
+        tight, joint, unsel, discs = (v["violations"] for v in r["per_obstacle"])
+        n = r["instance_steps"]
+        out.update(risk=dict(tight=tight / max(n, 1), joint=joint / max(n, 1), unselected=unsel / max(n, 1),
+                             mean_discs_violated=discs / max(n, 1), min_cbc=r["min_cbc"][0], instance_steps=n,
+                             max_risk=float(max_risk)),
+                   solved=risk["solved"], risk_counters={k: risk[k] for k in ops._FIELD_RISK_SUMS})
     if record:
         out.update(rec)
     return out

@@ -1557,6 +1557,39 @@ int bcbf_obstacle_field_commit_f32(float* x, const float* y, const int* status, 
 int bcbf_obstacle_field_commit_f64(double* x, const double* y, const int* status, const int* cert, int* status_eff, double dt,
                                    double L_true, int Bt, void* stream);
 
+/* bcbf_obstacle_field_commit_sampled (field_plant.hip; one wave per instance, as the audit): the commit on a plant DRAWN FROM
+ * THE MODEL'S OWN POSTERIOR, in place of bcbf_obstacle_field_commit.  Reference: ObstacleCBF, unicycle_move_to_pose.py:618-696;
+ * one un-relaxed cone per obstacle (`_cbcs`, :901-920); the program (:926-953); the plant fu_func_gp(u), :262-275, drawn as
+ * GaussianProcessBase.sample draws, gp_algebra.py:33-34; the condition on a state derivative, cbc1.py:10-14.
+ * status_eff[Bt] is written as the plain commit writes it.  An instance with status_eff = 0, in fp64 from the inputs as stored:
+ *     ubar = (1, u),  u = y as stored;   s = max(ubar' B_k ubar, 0);   A = L_A L_A' (a pivot <= 0 zeroes its column)
+ *     xdot_s = fhat + ghat u + M_k ubar + sqrt(s) L_A z          z[Bt,3]: the caller's standard normals (the library draws none)
+ *     for EVERY disc k of the field, at the state before the step:
+ *         cbc_k    = grad h_k . xdot_s + gamma h_k               (anything non-finite counts as -inf)
+ *         margin_k = the audit's margin  E_k - rho sqrt(max(s grad h_k' A grad h_k, 0))   (NaN counts as -inf)
+ *     x += xdot_s dt                                             (dt = 0: the state stays, everything else is done)
+ *   xdot_s[Bt,3];  cbc_min[Bt], cbc_argmin[Bt] (ties to the lower index);  tight_idx[Bt] = the disc of smallest margin_k (ties to
+ *   the lower index: the audit's ordering), cbc_tight[Bt] = that disc's cbc_k;  nneg[Bt] = the number of discs with cbc_k < 0.
+ *   Accumulators, in place (int32; min_cbc in T):  solved += 1, viol_tight += (cbc_tight < 0), viol_any += (nneg > 0),
+ *   viol_unselected += (a disc outside idx[b,:S] has cbc_k < 0), viol_discs += nneg, min_cbc = min(min_cbc, cbc_min).
+ *   The counts are taken on the fp64 values; every output is rounded to T once.
+ * Every other instance keeps its state bit for bit and its accumulators; it gets xdot_s = 0, cbc_min = cbc_tight = 0,
+ * cbc_argmin = tight_idx = -1, nneg = 0.  There is no L_true: the true drive plays no part.
+ * BCBF_EINVAL with a reason, before any HIP call, for: Bt <= 0, S outside 1..3, Kf outside S..BCBF_MAX_FIELD, field_stride not
+ * 0 / 1, gamma not finite, dt negative or not finite, any null pointer. */
+int bcbf_obstacle_field_commit_sampled_f32(
+    float* x, const float* y, const int* status, const int* cert, const float* Mk, const float* Bk, const float* A,
+    const float* fhat, const float* ghat, const float* rho, const float* centers_f, const float* radii_f, int field_stride,
+    const float* tw, float gamma, const int* idx, const float* z, int* status_eff, float* xdot_s, float* cbc_min,
+    int* cbc_argmin, int* tight_idx, float* cbc_tight, int* nneg, int* solved, int* viol_tight, int* viol_any,
+    int* viol_unselected, int* viol_discs, float* min_cbc, float dt, int Bt, int Kf, int S, void* stream);
+int bcbf_obstacle_field_commit_sampled_f64(
+    double* x, const double* y, const int* status, const int* cert, const double* Mk, const double* Bk, const double* A,
+    const double* fhat, const double* ghat, const double* rho, const double* centers_f, const double* radii_f, int field_stride,
+    const double* tw, double gamma, const int* idx, const double* z, int* status_eff, double* xdot_s, double* cbc_min,
+    int* cbc_argmin, int* tight_idx, double* cbc_tight, int* nneg, int* solved, int* viol_tight, int* viol_any,
+    int* viol_unselected, int* viol_discs, double* min_cbc, double dt, int Bt, int Kf, int S, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -6,9 +6,11 @@ as one captured graph per step.  Beside it, in the same process and alternating 
 the fused control step with the first three discs as its whole program, and the composed path (task rows ->
 terms -> generic cone solver -> plant step) with the seven discs of the Kf = 7 field.  One JSON line per configuration: the
 median, minimum and maximum wall time of `--repeat` runs after a warm-up run, each run ending in a device synchronise, per
-step and per instance-step; the certificate's counts.
+step and per instance-step; the certificate's counts.  `--plant posterior` adds, alternating with the others in the same rounds,
+the field loop on a plant drawn from the model's posterior (`plant="posterior"`: the commit evaluates every disc on the draw) with
+its risk rates -- tight, joint, unselected -- and writes profiles/obstacle_field_posterior_plant.json.
 
-    python tools/bench_obstacle_field.py [--quick] [--repeat 3] [--dtype float64] [--out profiles/obstacle_field.json]
+    python tools/bench_obstacle_field.py [--quick] [--repeat 3] [--dtype float64] [--plant posterior] [--out profiles/obstacle_field.json]
 """
 import json
 import math
@@ -105,25 +107,36 @@ def main():
     quick = "--quick" in sys.argv
     repeat = int(sys.argv[sys.argv.index("--repeat") + 1]) if "--repeat" in sys.argv else 3
     dtype = getattr(torch, sys.argv[sys.argv.index("--dtype") + 1]) if "--dtype" in sys.argv else torch.float64
-    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "obstacle_field.json")
+    plant = sys.argv[sys.argv.index("--plant") + 1] if "--plant" in sys.argv else "true"
+    if plant not in ("true", "posterior"):
+        sys.exit("--plant true | posterior")
+    default_out = "obstacle_field_posterior_plant.json" if plant == "posterior" else "obstacle_field.json"
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", default_out)
     Bt, steps = (256, 20) if quick else (4096, 200)
     fields = {Kf: random_obstacle_field(Kf, seed=Kf) for Kf in (3, 7, 16, 64, 256)}
     # every configuration once (warm-up: code objects, allocator, clocks), then `repeat` rounds that alternate all of them
     configs = [("field", Kf, mode) for Kf in fields for mode in ("eager", "graph")]
+    if plant == "posterior":
+        configs += [("field-posterior", Kf, mode) for Kf in fields for mode in ("eager", "graph")]
     configs += [("fused-3", 3, "eager"), ("fused-3", 3, "graph"), ("composed-7", 7, "eager")]
     times = {c: [] for c in configs}
     extra = {}
     for rnd in range(repeat + 1):
         for c in configs:
             name, Kf, mode = c
-            if name == "field":
-                r = obstacle_field_rollouts(Bt, fields[Kf], numSteps=steps, dt=DT, L_true=L_TRUE, dtype=dtype, use_graph=mode == "graph")
+            if name in ("field", "field-posterior"):
+                r = obstacle_field_rollouts(Bt, fields[Kf], numSteps=steps, dt=DT, L_true=L_TRUE, dtype=dtype, use_graph=mode == "graph",
+                                            plant="posterior" if name == "field-posterior" else "true")
                 secs = r["loop_seconds"]
                 n = Bt * steps
                 extra[c] = dict(certified_share=r["certified_steps"] / n, rounds_hist=r["rounds_hist"],
                                 uncertified_steps=r["uncertified_steps"], full_set_steps=r["full_set_steps"],
                                 unsolved_steps=r["unsolved_steps"], collisions=r["stats"]["collisions"],
                                 instances_with_a_step_not_taken=r["stats"]["solver_failures"], min_h=r["stats"]["min_h"])
+                if name == "field-posterior":
+                    extra[c].update(risk_tight=r["risk"]["tight"], risk_joint=r["risk"]["joint"], risk_unselected=r["risk"]["unselected"],
+                                    mean_discs_violated=r["risk"]["mean_discs_violated"], risk_instance_steps=r["risk"]["instance_steps"],
+                                    max_risk=r["risk"]["max_risk"])
             else:
                 secs, failures, collisions = plain_loop(Bt, fields[Kf], steps, dtype, mode == "graph")
                 extra[c] = dict(instances_with_a_step_not_taken=failures, collisions=collisions)
