@@ -82,8 +82,16 @@
 #ifndef BCBF_PS_SKIP_DEAD_A
 #define BCBF_PS_SKIP_DEAD_A 1
 #endif
+#ifndef BCBF_PS_TAIL
+#define BCBF_PS_TAIL 1       // fp32 control-step form (C = 3, values only): once the A side is dead, the whole block (32 columns) is
+                             // in flight per wave instead of 8 to 16 columns.  A stage's bytes shrink with the column length
+                             // (8 columns x (Np - 32 (J + 1)) rows); the A side's load registers are dead there, so the whole
+                             // block fits the registers the first loop holds.  (measured beside a form with 16
+                             // columns per stage down to 128 rows below the block -- this one is as fast on the part schedule
+                             // and faster in one launch)
+#endif
 #ifndef BCBF_PX_UNR32
-#define BCBF_PX_UNR32 8      // fp32 query + append column (4 right-hand-side columns): columns per pipeline stage
+#define BCBF_PX_UNR32 8     // fp32 query + append column (4 right-hand-side columns): columns per pipeline stage
 #endif
 #ifndef BCBF_PX_VALU32
 #define BCBF_PX_VALU32 1     // fp32 query + append column: per-lane Gram / mean sums instead of the matrix-core accumulator
@@ -400,6 +408,16 @@ posterior_step_kernel(const T* __restrict__ Lop, const T* __restrict__ Vw, const
                                   //  108-268 B per lane and streams at 0.32-0.46 of HBM, round 5)
                                   : (sizeof(T) == 8 && XC == 0 && (C >= 4 || NS > 4)) ? BCBF_PS_UNR64_WIDE : BCBF_PS_UNR)), NGRP = NB / UNR, HALF = NB / 2;
     static_assert(NGRP % 2 == 0, "pipeline processes two groups per trip");
+    // whole blocks in flight behind the A side (BCBF_PS_TAIL): the fp32 control-step form only -- every other form keeps its one depth
+    constexpr bool TAIL = BCBF_PS_TAIL && PK && !ONE && C == 3 && NS == 4 && NJ == 0 && NQ == 1 && !RHS && XC == 0 && !XK && UNR == 8;
+    // Depth of a stage (compile-time), in groups of UNR columns: 1 = both sides (every other form: always); NGRP = the whole block,
+    // B side only.  The whole-block stage keeps half of its B-side loads in the A side's registers of the same set: with AL false
+    // issue / consume touch `lb` alone, so handing them la0 / la1 as `lb` runs the group out of those registers.
+    using Depth1 = std::integral_constant<int, 1>;
+    using DepthBlock = std::integral_constant<int, NGRP>;
+    // first residual set (0 = A, NR - 1 = B) a B-only block publishes.  (A type, not a constant: block_body names it in an expression
+    // that depends on its AL -- a constant named there is captured by the lambda, which perturbs every instantiation's code.)
+    using FirstPublishedBOnly = std::integral_constant<int, TAIL ? NR - 1 : 0>;
     VecT la0[UNR], lb0[UNR], la1[UNR], lb1[UNR];
     T dval[HALF];
     const int di = tid & 31, dh = (tid >> 5) & 1;
@@ -470,7 +488,16 @@ posterior_step_kernel(const T* __restrict__ Lop, const T* __restrict__ Vw, const
             }
         }
     };
-    auto issue_diag = [&](int J) {      // inv(L_JJ)[di][dh*16 + q], wave 0 only (others, and the zeros above the
+    // B side only, 2 UNR columns -- groups g, g + 1 of block J -- through one set's registers (set 0: lb0 + la0, set 1: lb1 + la1)
+    auto issue2 = [&](VecT* la, VecT* lb, int J, int g) __attribute__((always_inline)) {
+        issue(la, lb, J, g, std::false_type{});
+        issue(la, la, J, g + 1, std::false_type{});
+    };
+    auto consume2 = [&](const VecT* la, const VecT* lb, int g) __attribute__((always_inline)) {
+        consume(la, lb, g * UNR, std::false_type{});
+        consume(la, la, (g + 1) * UNR, std::false_type{});
+    };
+    auto issue_diag = [&](int J) {     // inv(L_JJ)[di][dh*16 + q], wave 0 only (others, and the zeros above the
 #pragma unroll                          // diagonal, which are not stored: out of range -> 0, no traffic)
         for (int q = 0; q < HALF; ++q) {
             const int jj = dh * HALF + q;
@@ -499,11 +526,14 @@ posterior_step_kernel(const T* __restrict__ Lop, const T* __restrict__ Vw, const
     if (nblk > 1) issue(la0, lb0, 0, 0, std::true_type{});
     // One block of the forward substitution.  AL (compile-time): this wave still owns live A-side rows; the blocks after its last live
     // one run the B side only (BCBF_PS_SKIP_DEAD_A) -- in a SECOND loop, so that the A side's registers are dead there
-    auto block_body = [&](const int J, auto AL) __attribute__((always_inline)) {
+    // DN (compile-time): groups of UNR columns per pipeline stage in this block (1 everywhere but in the B-only loop of BCBF_PS_TAIL)
+    auto block_body = [&](const int J, auto AL, auto DN) __attribute__((always_inline)) {
         const int row0 = J * NB;
-        // 1. publish r_J
+        // 1. publish r_J  (BCBF_PS_TAIL: the B-only loop never publishes A-side rows -- the last of them went out before that
+        //    loop, so the A side's residuals are dead registers there)
+        constexpr int R0 = std::conditional_t<decltype(AL)::value, std::integral_constant<int, 0>, FirstPublishedBOnly>::value;
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
+        for (int r = R0; r < NR; ++r) {
             const int rb = r == 0 ? rbA : rbB;
             if (live && rb / RPB == J) {
 #pragma unroll
@@ -636,15 +666,52 @@ posterior_step_kernel(const T* __restrict__ Lop, const T* __restrict__ Vw, const
                     consume(la1, lb1, (g + 1) * UNR, AL);
                 }
             };
-            stream_block(AL);
+            constexpr int D = decltype(DN)::value;
+            if constexpr (D == 1) {
+                stream_block(AL);
+            } else {
+                // B only, the whole block is one stage: both sets are in flight when the block starts (they cross its two
+                // barriers and its diagonal step), and each is re-issued for the next block as soon as it has been consumed.
+                // (The re-issue is unconditional: a branch around it makes the wait in front of the next consume cover both
+                //  paths, that is, wait for the prefetch itself.  Below the last block with rows under it every lane's offset
+                //  is out of range: zeros, no traffic, never consumed.)
+                static_assert(!decltype(AL)::value && D == 4 && NGRP == 4, "whole-block stage: B side only, the two sets hold the block's four groups");
+                consume2(la0, lb0, 0);
+                issue2(la0, lb0, J + 1, 0);
+                consume2(la1, lb1, 2);
+                issue2(la1, lb1, J + 1, 2);
+            }
         }
     };
-    {
+    if constexpr (TAIL) {
+        // Two consecutive loops with compile-time depths (one loop with a run-time depth spills); the wave picks the bound:
+        //   [0, Jsplit)     both sides, UNR columns per stage.  A lane's A-side row block is its pair index, so the wave's A side is
+        //                   live in block J while (J + 1) RPB <= its largest LIVE pair index (lanes beyond npairs own nothing)
+        //   [Jsplit, nblk)  B side only, the whole block per stage
+        // At the hand-over block Jsplit's group 0 is in flight (the first loop's prefetch); its other three groups are issued
+        // here, before the block's first barrier (its loads do not depend on the blocks before it).
+        const int rbA_wave_max = min(__builtin_amdgcn_readfirstlane(tid) | 63, npairs - 1);
+        const int Jsplit = min(nblk, rbA_wave_max / RPB);
+        for (int J = 0; J < Jsplit; ++J) block_body(J, std::true_type{}, Depth1{});
+        if (Jsplit + 1 < nblk) {
+            issue(la0, la0, Jsplit, 1, std::false_type{});
+            issue2(la1, lb1, Jsplit, 2);
+        }
+        // The wave's last A-side rows lie in block Jsplit (rbA_wave_max / RPB): published here, so that the loop below holds no
+        // A-side residuals.  rbuf is free: its readers (block Jsplit - 1's diagonal step) finished before that block's second barrier.
+        if (live && rbA / RPB == Jsplit) {
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+#pragma unroll
+                for (int c = 0; c < CT; ++c) rbuf[rbA * V + v - Jsplit * NB][c] = BCBF_ACC(0, v, c);
+        }
+        for (int J = Jsplit; J < nblk; ++J) block_body(J, std::false_type{}, DepthBlock{});
+    } else {
         // a wave's A-side row blocks are [64 w, 64 w + 63]: live in block J while (J + 1) RPB <= the largest of them
         const int rbA_wave_max = __builtin_amdgcn_readfirstlane(tid) | 63;
         const int Jsplit = (BCBF_PS_SKIP_DEAD_A && !ONE) ? min(nblk, rbA_wave_max / RPB) : nblk;
-        for (int J = 0; J < Jsplit; ++J) block_body(J, std::true_type{});
-        for (int J = Jsplit; J < nblk; ++J) block_body(J, std::false_type{});
+        for (int J = 0; J < Jsplit; ++J) block_body(J, std::true_type{}, Depth1{});
+        for (int J = Jsplit; J < nblk; ++J) block_body(J, std::false_type{}, Depth1{});
     }
 
     if constexpr (XC > 0) {
